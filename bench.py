@@ -17,7 +17,13 @@ flat 78*16*16 head, 5.27 M params), random-init and then trained for ``--settle`
 untimed updates (default 500) so the timed window measures a training run's steady
 state; the JSON ``data`` field names the settle count.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs: set up, settle and warm up, time the K updates,
+print one JSON line (``ms_per_step`` = one timed update). ``--dump-outputs DIR`` then writes
+the arrays of one more, timing-independent step of the same path (``_reproducible_step``) as
+``DIR/<name>.npy``, identical from run to run; ``--full`` adds the
+measurements that take runs of their own (the sync-timed learner phase split).
 
 With ``--gpus N > 1`` and no torchrun environment, bench.py launches N ranks
 itself (``torch.distributed.run`` as a child process, parallel/launch.py) and
@@ -103,7 +109,82 @@ def parse(argv=None):
     p.add_argument("--report_every", type=int, default=0,
                    help="diagnostics: every k timed steps print the window's frames/s and active "
                         "cells per env to stderr (host clock; 0 = off)")
+    p.add_argument("--dump-outputs", dest="dump_outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps write the arrays one step of the timed path "
+                        "computes as DIR/<name>.npy (float32, rank 0): losses, the updated flat "
+                        "parameters and the rollout's behaviour log-prob / value / reward, at "
+                        "most 64 MB in all (a larger array is cut to a fixed seeded sample). The "
+                        "window's own steps depend on how the actor threads and the learner "
+                        "interleave, so the step that is written runs once more after the window, "
+                        "from the seeded initial weights on one env group's first rollout: the "
+                        "same arrays, bit for bit, in every run of one build")
+    p.add_argument("--full", action="store_true",
+                   help="everything beyond the headline figure: also runs the sync-timed learner "
+                        "update of --profile_phases after the window (learner_phase_s). A plain "
+                        "run sets up, warms up, times --steps updates and prints the result line")
     return p.parse_args(argv)
+
+
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: all files together
+DUMP_BATCH_KEYS = ("logp", "value", "reward")  # [unroll + 1, envs] fp32 rows of a rollout
+WGRAD_QUEUE_SITE = 4  # common.h kQueueWgrad
+
+
+def _dump_outputs(path, arrays, seed):
+    """Write ``arrays`` (name -> tensor) as ``path/<name>.npy`` in float32. Smallest first,
+    each array may take an even share of the byte budget still left; one over its share is
+    cut to a sorted, seeded sample of its flat view (the same elements for the same shapes
+    and seed)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BUDGET_BYTES // 4
+    order = sorted(arrays, key=lambda k: arrays[k].numel())
+    for n_after, name in zip(range(len(order), 0, -1), order):
+        a = arrays[name].detach().float().cpu().numpy()
+        share = left // n_after
+        left -= min(a.size, share)
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def _reproducible_step(args, make_model, dev, threads):
+    """One step of the timed path (rollout -> learner update -> publish) whose result does not
+    depend on thread timing, for ``--dump-outputs``. In the window, which weight version a
+    rollout acted with, the order the groups' rollouts arrive in and the weight gradient's
+    work-queue summation order all vary from run to run, and 500 updates of sampled actions
+    amplify that. Here a fresh learner starts from the seeded initial weights, a fresh engine
+    of one env group (the benchmark's envs_per_group x unroll, the same kernels and captured
+    graphs) acts its first rollout with exactly those weights, and the update runs with the
+    weight gradient's static stride (the queue's sums differ from it only in their order)."""
+    import torch
+
+    from microbeast_amd import _native
+    from microbeast_amd.learner import Learner, LearnerHParams
+    from microbeast_amd.runtime.gpu_actors import GpuActorRuntime
+
+    K = _native.kernels()
+    _native.check(K.mbk_set_work_queue_site(WGRAD_QUEUE_SITE, 0), "queue site")
+    torch.manual_seed(args.seed)
+    learner = Learner(make_model(), LearnerHParams(bucket_mb=args.bucket_mb,
+                                                   allreduce_dtype=args.allreduce_dtype), dev)
+    rt = GpuActorRuntime(make_model, args.size, 1, args.envs_per_group, args.unroll, 1, dev,
+                         n_threads=threads, seed=args.seed, fp8_policy=args.fp8_policy, n_lanes=1)
+    rt.start(learner.flat)
+    try:
+        batch, slots = rt.get_batch(timeout=120.0)
+        out = {f"batch_{k}": batch[k].clone() for k in DUMP_BATCH_KEYS}
+        out["losses"] = learner.learn(batch).clone()
+        rt.release(slots)
+        rt.publish(learner.flat, version=learner.n_updates)
+        torch.cuda.synchronize()
+        out["params"] = learner.flat.data.clone()
+    finally:
+        rt.close()
+        _native.check(K.mbk_set_work_queue_site(WGRAD_QUEUE_SITE, 1), "queue site")
+    return out
 
 
 def _occupancy(rt):
@@ -279,10 +360,13 @@ def main(argv=None):
     phase_ms = learner.phases.read()  # HIP-event split of the last timed update (no sync)
     occ = _occupancy(rt)
     phase = None
-    if args.profile_phases:
+    if args.profile_phases or args.full:
         learner.learn(rt.get_batch()[0], sync_timing=True)
         phase = learner.timing
     rt.stop()
+    if args.dump_outputs and info.is_main:
+        _dump_outputs(args.dump_outputs, _reproducible_step(args, make_model, dev, threads),
+                      args.seed)
     # every rank's actor side, so a weak-scaled N-GPU run shows which rank (if any) is
     # CPU-bound: env workers busy ~100 % of the time means the rank's CPU share, not the
     # GPU, sets its frame rate (each rank steps its own envs)

@@ -13,7 +13,7 @@ DP path does besides the collective kernel itself is pinned here first (VERDICT 
   writes one (train._gather_episodes + CsvLogger);
 * the rank-0 checkpoint behind a barrier restores the same model on every rank.
 
-Reference: the reference has no DP (/root/reference/microbeast.py:119,254-260 leaves its two
+Reference: the reference has no DP (its microbeast.py:119,254-260 leaves its two
 Hogwild learner threads commented out); SURVEY section 2.2 P5 and section 4 ("gloo ... world_size
 2-4"). Each case spawns its ranks once (a few seconds per rank to import torch).
 """

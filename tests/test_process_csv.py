@@ -15,7 +15,7 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/experiments/5_ener"
+REF = os.path.join(ROOT, "tests", "golden", "5_ener")  # the reference's log and its output
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
@@ -24,8 +24,6 @@ def _rows(path):
         return [r for r in csv.reader(f) if r]
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "5_enero_processed.csv")),
-                    reason="reference fixture not mounted")
 def test_matches_reference_processed_fixture(tmp_path):
     import process_csv
 
