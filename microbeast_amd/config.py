@@ -96,7 +96,11 @@ class Flags:
     checkpoint_every: int = 100   # updates
     resume: bool = False
     checkpoint: str = ""          # path for --test / --resume (default <savedir>/<exp>.ckpt)
-    eval_episodes: int = 10
+    eval_episodes: int = 10       # --test: the first N episodes to finish (ignored with --eval_envs)
+    eval_envs: int = 0            # --test: > 0 evaluates on that many envs, each contributing the
+                                  # first episode it finishes (on the GPU engine when a GPU is
+                                  # present); 0: the host-stepped --n_envs / --eval_episodes loop
+    eval_greedy: bool = False     # --test: arg-max actions instead of sampled ones
     allow_random_init: bool = False  # --test without a checkpoint: evaluate random weights
                                      # instead of failing
     batch_timeout: float = 600.0

@@ -97,6 +97,8 @@ typedef struct {
   uint32_t* abits;         // optional [E][S/32] active-cell bitmap of the row (bit c & 31 of
   uint32_t* abits2;        // word c >> 5: the cell's mask is non-zero), + the obs2 copy; the
                            // learner's head compaction then never reads the masks in full
+  int32_t greedy;          // 0: sample the actions (Philox); 1: arg-max actions (per segment the
+                           // lowest legal index at the legal maximum), no random numbers drawn
 } MbkActStep;
 
 int mbk_act_step(const MbkActModel* m, const MbkActStep* s, hipStream_t stream);

@@ -117,11 +117,17 @@ __device__ __forceinline__ float u01(uint32_t x) {  // (0,1]
 // log-prob 0 and entropy 0 in fp32 (as in the reference); we sample index 0
 // there (the env ignores it — no unit to command).
 //
-// mode 0 = score the given actions; mode 1 = sample (writes actions).
-template <typename ZPtr>
+// mode 0 = score the given actions; mode 1 = sample (writes actions); mode 2 = greedy (writes
+// actions: per segment the lowest legal index whose logit equals the legal maximum, i.e.
+// argmax(where(mask, z, -1e8)) with the first occurrence on ties, ops/cell_head.py greedy; u is
+// not read). Modes 0 / 1 are the run-time `sample` of the GREEDY = false instantiation; greedy
+// is a compile-time mode (GREEDY = true, `sample` ignored) so that the scoring / sampling
+// instantiations carry no extra branch or register.
+template <bool GREEDY = false, typename ZPtr>
 __device__ __forceinline__ void cell_forward(const ZPtr z, const uint32_t m[3], uint8_t* act,
                                              bool sample, const float u[kComps], float* logp_out,
                                              float* ent_out) {
+  if constexpr (GREEDY) sample = true;
   uint32_t m0 = m[0], m1 = m[1], m2 = m[2];
   asm volatile("" : "+v"(m0), "+v"(m1), "+v"(m2));  // opaque: no array to re-index
   float lp = 0.f, ent = 0.f;
@@ -147,7 +153,12 @@ __device__ __forceinline__ void cell_forward(const ZPtr z, const uint32_t m[3], 
     const float lse = mx + __logf(s);
     ent += lse - sz * inv;  // -sum p log p = lse - sum p z
     int a;
-    if (sample) {
+    if constexpr (GREEDY) {
+      a = 0;
+      for (int j = n - 1; j >= 0; --j)
+        if (mask_bit3(m0, m1, m2, off + j) && (float)z[off + j] == mx) a = j;
+      act[k] = (uint8_t)a;
+    } else if (sample) {
       const float target = u[k] * s;
       float c = 0.f;
       a = -1;

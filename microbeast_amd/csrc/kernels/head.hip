@@ -343,6 +343,8 @@ __device__ __forceinline__ void unit_prefix(const int* __restrict__ cnt, int S, 
 // the per-cell bucket counts (a 16-pair-unit prefix over the S cells in LDS, then a binary
 // search per unit) -- head_units_kernel's unit_cell / unit_row / grp_* / totals without its
 // launch; the counters are reset by the step's last launch (row_sum_pack).
+// GREEDY: mode 2 (arg-max actions, no random numbers); else `sample` is mode 0 / 1 at run time.
+template <bool GREEDY>
 __global__ __launch_bounds__(256) void head_fwd_kernel(
     const bf16* __restrict__ X, const bf16* __restrict__ Wp, const float* __restrict__ bp,
     const uint32_t* __restrict__ mask, uint8_t* __restrict__ action, const uint64_t* __restrict__ rng,
@@ -391,7 +393,8 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(
       uint32_t m[3] = {mask[fc * 3], mask[fc * 3 + 1], mask[fc * 3 + 2]};
       uint8_t a[kComps];
       float uu[kComps];
-      if (sample) {
+      if constexpr (GREEDY) {
+      } else if (sample) {
         const uint64_t seed = rng[0], step = rng[1];
         u32x4 ctr = {(uint32_t)fc, (uint32_t)(fc >> 32), (uint32_t)step, (uint32_t)(step >> 32)};
         u32x4 q0 = philox(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
@@ -404,8 +407,8 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(
         for (int k = 0; k < kComps; ++k) a[k] = action[fc * kComps + k];
       }
       float lp, ent;
-      cell_forward(&z[lane][0], m, a, sample != 0, uu, &lp, &ent);
-      if (sample) {
+      cell_forward<GREEDY>(&z[lane][0], m, a, sample != 0, uu, &lp, &ent);
+      if (GREEDY || sample) {
 #pragma unroll
         for (int k = 0; k < kComps; ++k) action[fc * kComps + k] = a[k];
       }
@@ -499,6 +502,7 @@ __device__ __forceinline__ void job_prefix(const int* __restrict__ cnt, int S, i
   if (lane == 63) jpre[kMaxUnitCells] = x;
 }
 
+template <bool GREEDY>
 __device__ __forceinline__ void head_act_kernel_body(const HeadActArgs& a) {
   __shared__ float zs[HA_NW][HA_JOB * HA_ZS];
   __shared__ int jpre[kMaxUnitCells + 1];
@@ -581,14 +585,16 @@ __device__ __forceinline__ void head_act_kernel_body(const HeadActArgs& a) {
     if (mine) {
       uint8_t act[kComps];
       float uu[kComps];
-      u32x4 ctr = {(uint32_t)fc, (uint32_t)(fc >> 32), (uint32_t)step, (uint32_t)(step >> 32)};
-      u32x4 q0 = philox(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
-      ctr.y ^= 0x80000000u;
-      u32x4 q1 = philox(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
-      uu[0] = u01(q0.x); uu[1] = u01(q0.y); uu[2] = u01(q0.z); uu[3] = u01(q0.w);
-      uu[4] = u01(q1.x); uu[5] = u01(q1.y); uu[6] = u01(q1.z);
+      if constexpr (!GREEDY) {
+        u32x4 ctr = {(uint32_t)fc, (uint32_t)(fc >> 32), (uint32_t)step, (uint32_t)(step >> 32)};
+        u32x4 q0 = philox(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
+        ctr.y ^= 0x80000000u;
+        u32x4 q1 = philox(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
+        uu[0] = u01(q0.x); uu[1] = u01(q0.y); uu[2] = u01(q0.z); uu[3] = u01(q0.w);
+        uu[4] = u01(q1.x); uu[5] = u01(q1.y); uu[6] = u01(q1.z);
+      }
       float lp, en;
-      cell_forward(zt + lane * HA_ZS, m, act, true, uu, &lp, &en);
+      cell_forward<GREEDY>(zt + lane * HA_ZS, m, act, true, uu, &lp, &en);
 #pragma unroll
       for (int k = 0; k < kComps; ++k) a.action[fc * kComps + k] = act[k];
       const uint64_t x = (uint64_t)__float_as_uint(lp) |
@@ -636,7 +642,11 @@ __device__ __forceinline__ void head_act_kernel_body(const HeadActArgs& a) {
 }
 // thin wrapper: the body takes the arguments by const reference (conv0_row_kernel, profile 43)
 __global__ __launch_bounds__(64 * HA_NW, 2) void head_act_kernel(HeadActArgs a) {
-  head_act_kernel_body(a);
+  head_act_kernel_body<false>(a);
+}
+// MbkActStep.greedy: the same step with arg-max actions (no Philox draws)
+__global__ __launch_bounds__(64 * HA_NW, 2) void head_act_greedy_kernel(HeadActArgs a) {
+  head_act_kernel_body<true>(a);
 }
 
 // logp[f] = sum over f's active cells of the pair log-probs (ent likewise), in cell order
@@ -1613,25 +1623,38 @@ extern "C" int mbk_head_fwd(const void* X, const void* Wp, const float* bp, cons
                             const int* unit_cell, const int* unit_row, const int* grp_start,
                             const int* grp_count, const int* totals, int S, int grid,
                             float* cell_lp, float* cell_ent, int pair_out, hipStream_t stream) {
-  hipLaunchKernelGGL(head_fwd_kernel, dim3(grid), dim3(256), 0, stream, (const bf16*)X,
-                     (const bf16*)Wp, bp, mask, action, rng, sample, pairs, unit_cell, unit_row,
-                     grp_start, grp_count, totals, S, cell_lp, cell_ent, pair_out,
-                     (const int*)nullptr, 0);
+  if (sample < 0 || sample > 2) return (int)hipErrorInvalidValue;
+  if (sample == 2)
+    hipLaunchKernelGGL(head_fwd_kernel<true>, dim3(grid), dim3(256), 0, stream, (const bf16*)X,
+                       (const bf16*)Wp, bp, mask, action, rng, sample, pairs, unit_cell, unit_row,
+                       grp_start, grp_count, totals, S, cell_lp, cell_ent, pair_out,
+                       (const int*)nullptr, 0);
+  else
+    hipLaunchKernelGGL(head_fwd_kernel<false>, dim3(grid), dim3(256), 0, stream, (const bf16*)X,
+                       (const bf16*)Wp, bp, mask, action, rng, sample, pairs, unit_cell, unit_row,
+                       grp_start, grp_count, totals, S, cell_lp, cell_ent, pair_out,
+                       (const int*)nullptr, 0);
   return (int)hipGetLastError();
 }
 
 // Acting head on decode-bucketed pairs (cell c's pairs at bucket[c * E, + cnt[c])) without
 // head_units: every workgroup derives the 16-pair units from cnt (left for the caller to
-// reset: mbk_row_sum_pack's cnt argument). S <= 1024.
+// reset: mbk_row_sum_pack's cnt argument). S <= 1024. greedy: arg-max actions (mode 2).
 extern "C" int mbk_head_fwd_counts(const void* X, const void* Wp, const float* bp,
                                    const uint32_t* mask, uint8_t* action, const uint64_t* rng,
                                    const int* bucket, const int* cnt, int E, int S, int grid,
-                                   float* cell_lp, hipStream_t stream) {
+                                   float* cell_lp, int greedy, hipStream_t stream) {
   if (S < 1 || S > kMaxUnitCells - 1 || !cnt) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(head_fwd_kernel, dim3(grid), dim3(256), 0, stream, (const bf16*)X,
-                     (const bf16*)Wp, bp, mask, action, rng, 1, bucket, (const int*)nullptr,
-                     (const int*)nullptr, (const int*)nullptr, (const int*)nullptr,
-                     (const int*)nullptr, S, cell_lp, (float*)nullptr, 0, cnt, E);
+  if (greedy)
+    hipLaunchKernelGGL(head_fwd_kernel<true>, dim3(grid), dim3(256), 0, stream, (const bf16*)X,
+                       (const bf16*)Wp, bp, mask, action, rng, 2, bucket, (const int*)nullptr,
+                       (const int*)nullptr, (const int*)nullptr, (const int*)nullptr,
+                       (const int*)nullptr, S, cell_lp, (float*)nullptr, 0, cnt, E);
+  else
+    hipLaunchKernelGGL(head_fwd_kernel<false>, dim3(grid), dim3(256), 0, stream, (const bf16*)X,
+                       (const bf16*)Wp, bp, mask, action, rng, 1, bucket, (const int*)nullptr,
+                       (const int*)nullptr, (const int*)nullptr, (const int*)nullptr,
+                       (const int*)nullptr, S, cell_lp, (float*)nullptr, 0, cnt, E);
   return (int)hipGetLastError();
 }
 
@@ -1805,8 +1828,8 @@ extern "C" int mbk_act_head(const MbkActModel* m, const MbkActStep* s, hipStream
   }
   // three 2-wave workgroups per CU (the LDS logit tiles allow three): ~1500 waves for the
   // ~800 64-pair jobs of a settled 8192-env step
-  hipLaunchKernelGGL(head_act_kernel, dim3(std::max(1, cus * 6 / HA_NW)), dim3(64 * HA_NW), 0,
-                     stream, a);
+  hipLaunchKernelGGL(s->greedy ? head_act_greedy_kernel : head_act_kernel,
+                     dim3(std::max(1, cus * 6 / HA_NW)), dim3(64 * HA_NW), 0, stream, a);
   return (int)hipGetLastError();
 }
 

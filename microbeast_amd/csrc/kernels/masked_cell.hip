@@ -52,7 +52,8 @@ __device__ __forceinline__ void stage_active(const TZ* __restrict__ logits, int6
   }
 }
 
-template <typename TZ>
+// GREEDY: mode 2 (arg-max actions, no random numbers); else `sample` is mode 0 / 1 at run time
+template <typename TZ, bool GREEDY = false>
 __global__ __launch_bounds__(kTile) void masked_cell_fwd_kernel(
     const TZ* __restrict__ logits, const uint32_t* __restrict__ mask, uint8_t* __restrict__ action,
     const uint64_t* __restrict__ rng, int sample, int64_t ncells, float* __restrict__ cell_logp,
@@ -69,7 +70,8 @@ __global__ __launch_bounds__(kTile) void masked_cell_fwd_kernel(
   if (i >= nc) return;
   uint8_t a[kComps];
   float u[kComps];
-  if (sample) {
+  if constexpr (GREEDY) {
+  } else if (sample) {
     const uint64_t seed = rng[0], step = rng[1];
     u32x4 c = {(uint32_t)cell, (uint32_t)(cell >> 32), (uint32_t)step, (uint32_t)(step >> 32)};
     u32x4 r0 = philox(c, (uint32_t)seed, (uint32_t)(seed >> 32));
@@ -82,8 +84,8 @@ __global__ __launch_bounds__(kTile) void masked_cell_fwd_kernel(
     for (int k = 0; k < kComps; ++k) a[k] = action[cell * kComps + k];
   }
   float lp, ent;
-  cell_forward(zs + i * kRow, m, a, sample != 0, u, &lp, &ent);
-  if (sample) {
+  cell_forward<GREEDY>(zs + i * kRow, m, a, sample != 0, u, &lp, &ent);
+  if (GREEDY || sample) {
 #pragma unroll
     for (int k = 0; k < kComps; ++k) action[cell * kComps + k] = a[k];
   }
@@ -163,6 +165,7 @@ __device__ __forceinline__ void stage_rows(const __hip_bfloat16* __restrict__ Z,
   }
 }
 
+template <bool GREEDY = false>
 __global__ __launch_bounds__(kTile) void masked_cell_rows_fwd_kernel(
     const __hip_bfloat16* __restrict__ Z, int ld, const int* __restrict__ rowcell,
     const int* __restrict__ totals, const uint32_t* __restrict__ mask, uint8_t* __restrict__ action,
@@ -181,7 +184,8 @@ __global__ __launch_bounds__(kTile) void masked_cell_rows_fwd_kernel(
     const uint32_t m[3] = {mask[cell * 3 + 0], mask[cell * 3 + 1], mask[cell * 3 + 2]};
     uint8_t a[kComps];
     float u[kComps];
-    if (sample) {  // same Philox stream as the dense kernel: keyed by the cell index
+    if constexpr (GREEDY) {
+    } else if (sample) {  // same Philox stream as the dense kernel: keyed by the cell index
       const uint64_t seed = rng[0], step = rng[1];
       u32x4 c = {(uint32_t)cell, (uint32_t)(cell >> 32), (uint32_t)step, (uint32_t)(step >> 32)};
       u32x4 q0 = philox(c, (uint32_t)seed, (uint32_t)(seed >> 32));
@@ -194,8 +198,8 @@ __global__ __launch_bounds__(kTile) void masked_cell_rows_fwd_kernel(
       for (int k = 0; k < kComps; ++k) a[k] = action[cell * kComps + k];
     }
     float lp, ent;
-    cell_forward(zs + i * kRow, m, a, sample != 0, u, &lp, &ent);
-    if (sample) {
+    cell_forward<GREEDY>(zs + i * kRow, m, a, sample != 0, u, &lp, &ent);
+    if (GREEDY || sample) {
 #pragma unroll
       for (int k = 0; k < kComps; ++k) action[cell * kComps + k] = a[k];
     }
@@ -268,15 +272,17 @@ extern "C" int mbk_masked_cell_fwd(const void* logits, int logits_bf16, const ui
                                    uint8_t* action, const uint64_t* rng, int sample,
                                    int64_t ncells, float* cell_logp, float* cell_ent,
                                    hipStream_t stream) {
+  if (sample < 0 || sample > 2) return (int)hipErrorInvalidValue;
   dim3 grid((unsigned)((ncells + kTile - 1) / kTile));
-  if (logits_bf16)
-    hipLaunchKernelGGL(masked_cell_fwd_kernel<__hip_bfloat16>, grid, dim3(kTile), 0, stream,
-                       (const __hip_bfloat16*)logits, mask, action, rng, sample, ncells, cell_logp,
-                       cell_ent, Lay{1, 0, kCell});
-  else
-    hipLaunchKernelGGL(masked_cell_fwd_kernel<float>, grid, dim3(kTile), 0, stream,
-                       (const float*)logits, mask, action, rng, sample, ncells, cell_logp, cell_ent,
-                       Lay{1, 0, kCell});
+#define MBK_FWD(TZ, GREEDY)                                                                    \
+  hipLaunchKernelGGL((masked_cell_fwd_kernel<TZ, GREEDY>), grid, dim3(kTile), 0, stream,       \
+                     (const TZ*)logits, mask, action, rng, sample, ncells, cell_logp, cell_ent, \
+                     Lay{1, 0, kCell})
+  if (logits_bf16 && sample == 2) MBK_FWD(__hip_bfloat16, true);
+  else if (logits_bf16) MBK_FWD(__hip_bfloat16, false);
+  else if (sample == 2) MBK_FWD(float, true);
+  else MBK_FWD(float, false);
+#undef MBK_FWD
   return (int)hipGetLastError();
 }
 
@@ -286,11 +292,17 @@ extern "C" int mbk_masked_cell_fwd_pbc(const void* logits, int cps, int n, int l
                                        int sample, int64_t ncells, float* cell_logp,
                                        float* cell_ent, hipStream_t stream) {
   if (ncells <= 0) return 0;
-  if (ld < kCell || ncells != (int64_t)cps * n) return (int)hipErrorInvalidValue;
+  if (ld < kCell || ncells != (int64_t)cps * n || sample < 0 || sample > 2)
+    return (int)hipErrorInvalidValue;
   dim3 grid((unsigned)((ncells + kTile - 1) / kTile));
-  hipLaunchKernelGGL(masked_cell_fwd_kernel<__hip_bfloat16>, grid, dim3(kTile), 0, stream,
-                     (const __hip_bfloat16*)logits, mask, action, rng, sample, ncells, cell_logp,
-                     cell_ent, Lay{cps, n, ld});
+  if (sample == 2)
+    hipLaunchKernelGGL((masked_cell_fwd_kernel<__hip_bfloat16, true>), grid, dim3(kTile), 0,
+                       stream, (const __hip_bfloat16*)logits, mask, action, rng, sample, ncells,
+                       cell_logp, cell_ent, Lay{cps, n, ld});
+  else
+    hipLaunchKernelGGL(masked_cell_fwd_kernel<__hip_bfloat16>, grid, dim3(kTile), 0, stream,
+                       (const __hip_bfloat16*)logits, mask, action, rng, sample, ncells, cell_logp,
+                       cell_ent, Lay{cps, n, ld});
   return (int)hipGetLastError();
 }
 
@@ -354,10 +366,16 @@ extern "C" int mbk_masked_cell_rows_fwd(const void* Z, int ld, const int* rowcel
                                         const int* totals, int nblk, const uint32_t* mask,
                                         uint8_t* action, const uint64_t* rng, int sample,
                                         float* cell_logp, float* cell_ent, hipStream_t stream) {
-  if (ld < kCell || ld % 8 || nblk < 1) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(masked_cell_rows_fwd_kernel, dim3(nblk), dim3(kTile), 0, stream,
-                     (const __hip_bfloat16*)Z, ld, rowcell, totals, mask, action, rng, sample,
-                     cell_logp, cell_ent);
+  if (ld < kCell || ld % 8 || nblk < 1 || sample < 0 || sample > 2)
+    return (int)hipErrorInvalidValue;
+  if (sample == 2)
+    hipLaunchKernelGGL(masked_cell_rows_fwd_kernel<true>, dim3(nblk), dim3(kTile), 0, stream,
+                       (const __hip_bfloat16*)Z, ld, rowcell, totals, mask, action, rng, sample,
+                       cell_logp, cell_ent);
+  else
+    hipLaunchKernelGGL(masked_cell_rows_fwd_kernel<false>, dim3(nblk), dim3(kTile), 0, stream,
+                       (const __hip_bfloat16*)Z, ld, rowcell, totals, mask, action, rng, sample,
+                       cell_logp, cell_ent);
   return (int)hipGetLastError();
 }
 

@@ -345,6 +345,8 @@ PYBIND11_MODULE(_mbrt, m) {
            py::arg("opp_blocks") = std::vector<py::bytes>{})
       .def("act_mode", &GpuEngine::act_mode)
       .def("set_sparse_io", &GpuEngine::set_sparse_io)
+      .def("set_greedy", &GpuEngine::set_greedy)
+      .def("greedy", &GpuEngine::greedy)
       .def("sparse_io", &GpuEngine::sparse_io)
       .def_static("act_model_size", [] { return (int)sizeof(MbkActModel); })
       .def("inject_fault", &GpuEngine::inject_fault)

@@ -201,6 +201,7 @@ void GpuEngine::start(const std::vector<LaneGraphs>& graphs) {
     L.pack_graph[0] = (hipGraphExec_t)g.pack;
     L.pack_graph[1] = (hipGraphExec_t)g.opp_pack;
   }
+  started_ = true;
   running_.store(true);
   for (int w = 0; w < cfg_.n_threads; ++w) workers_.emplace_back(&GpuEngine::worker_loop, this, w);
   driver_ = std::thread(&GpuEngine::driver_loop, this);
@@ -226,6 +227,11 @@ void GpuEngine::alloc_rows() {
     std::memset(h_code_list_p1_, 0, bytes);
     env_->write_code_lists(h_code_list_p1_, list_stride_, 1);
   }
+}
+
+void GpuEngine::set_greedy(bool on) {
+  if (started_ || running_.load()) throw std::runtime_error("set_greedy: engine already started");
+  greedy_ = on;
 }
 
 void GpuEngine::set_sparse_io(bool on) {
@@ -517,6 +523,7 @@ bool GpuEngine::enqueue_gpu(int g) {
       a.done_dst = (uint8_t*)u8_at(buf_.done, rs, ri);
     }
     a.step = L.act_step++;
+    a.greedy = greedy_ ? 1 : 0;
     act_active_cells_.fetch_add(G.idle.load(std::memory_order_relaxed), std::memory_order_relaxed);
     act_steps_.fetch_add(1, std::memory_order_relaxed);
     {

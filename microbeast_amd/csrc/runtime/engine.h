@@ -199,6 +199,12 @@ class GpuEngine {
   // the workers' action rows -- no H2D / D2H blit copies of dense [S] code rows
   void set_sparse_io(bool on);
   bool sparse_io() const { return sparse_; }
+  // greedy acting (evaluation): the fused player-0 step takes the arg-max action of every
+  // segment instead of sampling (MbkActStep.greedy); the self-play opponent's steps still
+  // sample. A captured policy graph has its mode baked in by whoever captured it. Before
+  // start() only: throws once the engine was started.
+  void set_greedy(bool on);
+  bool greedy() const { return greedy_; }
   const EngineConfig& config() const { return cfg_; }
   VecEnv& env() { return *env_; }
   bool failed() const { return failed_.load(); }
@@ -291,6 +297,8 @@ class GpuEngine {
   std::condition_variable work_cv_;
   std::atomic<uint64_t> work_epoch_{0};
   std::atomic<bool> running_{false};
+  bool started_ = false;  // start() was called (set_greedy is refused from then on)
+  bool greedy_ = false;
   std::atomic<bool> failed_{false};
   std::atomic<int> inject_fault_{0};
   mutable std::mutex err_m_;

@@ -305,8 +305,9 @@ class Agent(nn.Module):
     @torch.no_grad()
     def act(self, obs, mask_bits, rng_state=None, generator=None, action_out=None,
             logp_out=None, bucketed: bool = False, logits_out=None, value_out=None,
-            act16_out=None):
+            act16_out=None, greedy: bool = False):
         """Sample under the mask. Returns (action [N,S,7] u8, logp [N], value [N]).
+        greedy: the arg-max action of every component instead of a sampled one (evaluation).
         bucketed: the head's active pairs were bucketed by mbk_decode_obs_mask_bucket.
         logits_out: also write the dense policy logits [N, 78*h*w] (reference 'policy_logits';
         one extra dense head GEMM on gemm.hip, the sparse sampler does not need them)."""
@@ -325,12 +326,13 @@ class Agent(nn.Module):
             action, logp = sparse_sample(f.to(torch.bfloat16), self.actor.weight, self.actor.bias,
                                          mask_bits.reshape(n, -1, 3), rng_state,
                                          self._head(f.device), action_out, logp_out,
-                                         prepacked=pre, bucketed=bucketed, act16_out=act16_out)
+                                         prepacked=pre, bucketed=bucketed, act16_out=act16_out,
+                                         greedy=greedy)
             return action, logp, value
         logits, value = self.policy_value(obs)
         if logits_out is not None:
             logits_out.copy_(logits.float())
-        action, logp = cell_head.sample(logits, mask_bits, rng_state, generator)
+        action, logp = cell_head.sample(logits, mask_bits, rng_state, generator, greedy=greedy)
         return action, logp, value
 
     def evaluate(self, obs, mask_bits, action, n_score: int | None = None, abits=None):

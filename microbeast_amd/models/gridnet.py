@@ -111,21 +111,23 @@ class GridNetAgent(nn.Module):
 
     @torch.no_grad()
     def act(self, obs, mask_bits, rng_state=None, generator=None, action_out=None,
-            cell_logp=None, logp_out=None):
+            cell_logp=None, logp_out=None, greedy: bool = False):
+        """Sample under the mask (greedy: arg-max actions). (action, logp, value)."""
         if self._use_hip(obs):
             n = obs.numel() // (self.h * self.w)
             if self.sparse_logits:
                 cells = Cells(mask_bits, n, self.h * self.w)
                 zc, value = self.policy_value_pbc(obs, cells=cells)
                 action, logp = cell_head.sample_rows(zc, cells, mask_bits, rng_state, generator,
-                                                     action_out, cell_logp, logp_out)
+                                                     action_out, cell_logp, logp_out,
+                                                     greedy=greedy)
                 return action, logp, value
             lg, value = self.policy_value_pbc(obs)
             action, logp = cell_head.sample_pbc(lg, mask_bits, rng_state, generator, action_out,
-                                                cell_logp, logp_out)
+                                                cell_logp, logp_out, greedy=greedy)
             return action, logp, value
         logits, value = self.policy_value(obs)
-        action, logp = cell_head.sample(logits, mask_bits, rng_state, generator)
+        action, logp = cell_head.sample(logits, mask_bits, rng_state, generator, greedy=greedy)
         return action, logp, value
 
     def evaluate(self, obs, mask_bits, action, n_score: int | None = None):

@@ -45,7 +45,7 @@ class MbkActStep(ctypes.Structure):
                 ("act16", c_void_p), ("act_list", c_void_p), ("list_stride", c_int),
                 ("reward_src", c_void_p), ("done_src", c_void_p), ("reward_dst", c_void_p),
                 ("done_dst", c_void_p), ("step", ctypes.c_uint64), ("abits", c_void_p),
-                ("abits2", c_void_p)]
+                ("abits2", c_void_p), ("greedy", ctypes.c_int32)]
 
 
 def code_lists(codes: torch.Tensor, res: torch.Tensor, stride: int) -> torch.Tensor:
@@ -139,7 +139,8 @@ class ActWorkspace:
 
     def step(self, codes, res, obs, mask, action, logp, value, act16, obs2=None, mask2=None,
              reward=None, done=None, reward_dst=None, done_dst=None, code_list=None,
-             act_list=None, step: int | None = None, abits=None, abits2=None) -> None:
+             act_list=None, step: int | None = None, abits=None, abits2=None,
+             greedy: bool = False) -> None:
         """One fused policy step on the current stream. codes int16 [E, S], res int32 [E]
         (or code_list int32 [E, stride] sparse rows, ``code_lists``); outputs obs int32 [E, S],
         mask int32 [E, S, 3], action uint8 [E, S, 7], logp / value fp32 [E], act16 int16
@@ -147,7 +148,7 @@ class ActWorkspace:
         destination and the reward / done copy of the previous env step. step: the Philox
         step (default: the device counter rng[1], one host sync; the engine counts steps per
         lane itself). abits / abits2: int32 [E, S/32] active-cell bitmap rows to write (the learner's head
-        compaction input), abits2 with obs2."""
+        compaction input), abits2 with obs2. greedy: arg-max actions, no random numbers."""
         s = MbkActStep()
         s.codes, s.res = N.ptr(codes), N.ptr(res)
         s.code_list, s.act_list = N.ptr(code_list), N.ptr(act_list)
@@ -161,5 +162,6 @@ class ActWorkspace:
         s.step = int(self.rng[1]) if step is None else int(step)
         s.reward_dst, s.done_dst = N.ptr(reward_dst), N.ptr(done_dst)
         s.abits, s.abits2 = N.ptr(abits), N.ptr(abits2)
+        s.greedy = int(greedy)
         N.check(N.kernels().mbk_act_step(ctypes.addressof(self.struct), ctypes.addressof(s),
                                          N.stream_ptr()), "act_step")

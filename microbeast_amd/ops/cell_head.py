@@ -87,8 +87,9 @@ def _cells(logits: torch.Tensor) -> tuple[int, int]:
 
 def sample_gpu(logits: torch.Tensor, mask_bits: torch.Tensor, rng_state: torch.Tensor,
                action_out: torch.Tensor | None = None, cell_logp: torch.Tensor | None = None,
-               logp_out: torch.Tensor | None = None):
-    """Sample actions on device. rng_state: uint64-as-int64 [2] = (seed, step)."""
+               logp_out: torch.Tensor | None = None, greedy: bool = False):
+    """Sample actions on device. rng_state: uint64-as-int64 [2] = (seed, step). greedy: the
+    arg-max action of every segment instead (no random numbers; the step still advances)."""
     k = N.kernels()
     logits = logits.contiguous()
     n, nc = _cells(logits)
@@ -102,7 +103,8 @@ def sample_gpu(logits: torch.Tensor, mask_bits: torch.Tensor, rng_state: torch.T
     st = N.stream_ptr()
     N.check(k.mbk_masked_cell_fwd(logits.data_ptr(), int(logits.dtype == torch.bfloat16),
                                   mask_bits.data_ptr(), action_out.data_ptr(), rng_state.data_ptr(),
-                                  1, nc, cell_logp.data_ptr(), None, st), "masked_cell_fwd")
+                                  2 if greedy else 1, nc, cell_logp.data_ptr(), None, st),
+            "masked_cell_fwd")
     N.check(k.mbk_row_sum(cell_logp.data_ptr(), n, nc // n, logp_out.data_ptr(), st), "row_sum")
     N.check(k.mbk_rng_advance(rng_state.data_ptr(), st), "rng_advance")
     return action_out, logp_out
@@ -210,13 +212,12 @@ def score_pbc(logits: torch.Tensor, mask_bits: torch.Tensor, action: torch.Tenso
 
 def sample_pbc(logits: torch.Tensor, mask_bits: torch.Tensor, rng_state: torch.Tensor | None = None,
                generator: torch.Generator | None = None, action_out=None, cell_logp=None,
-               logp_out=None):
-    """(action [n,S,7] uint8, logp [n]) sampled from pixel-major logits [S][n][ld]."""
+               logp_out=None, greedy: bool = False):
+    """(action [n,S,7] uint8, logp [n]) sampled (greedy: arg-max) from pixel-major logits
+    [S][n][ld]."""
     S, n, ld = logits.shape
     if not logits.is_cuda:
-        with torch.no_grad():
-            a, lp, _ = cell_head_torch(_pbc_cm(logits), mask_bits, None, generator)
-        return a, lp
+        return _sample_torch(_pbc_cm(logits), mask_bits, generator, greedy)
     k = N.kernels()
     nc = S * n
     dev = logits.device
@@ -230,8 +231,9 @@ def sample_pbc(logits: torch.Tensor, mask_bits: torch.Tensor, rng_state: torch.T
     assert action_out.numel() == nc * COMPS and cell_logp.numel() >= nc
     st = N.stream_ptr()
     N.check(k.mbk_masked_cell_fwd_pbc(logits.data_ptr(), S, n, ld, mask_bits.contiguous().data_ptr(),
-                                      action_out.data_ptr(), rng_state.data_ptr(), 1, nc,
-                                      cell_logp.data_ptr(), None, st), "masked_cell_fwd_pbc")
+                                      action_out.data_ptr(), rng_state.data_ptr(),
+                                      2 if greedy else 1, nc, cell_logp.data_ptr(), None, st),
+            "masked_cell_fwd_pbc")
     N.check(k.mbk_row_sum_rng(cell_logp.data_ptr(), n, S, logp_out.data_ptr(),
                               rng_state.data_ptr(), st), "row_sum_rng")
     return action_out, logp_out
@@ -315,14 +317,12 @@ def score_rows(Zc: torch.Tensor, cells, mask_bits: torch.Tensor, action: torch.T
 
 def sample_rows(Zc: torch.Tensor, cells, mask_bits: torch.Tensor,
                 rng_state: torch.Tensor | None = None, generator: torch.Generator | None = None,
-                action_out=None, cell_logp=None, logp_out=None):
+                action_out=None, cell_logp=None, logp_out=None, greedy: bool = False):
     """(action [n,S,7] uint8, logp [n]) sampled from compact active-cell logits (same Philox
-    draws as the dense kernel: keyed by cell index)."""
+    draws as the dense kernel: keyed by cell index); greedy: arg-max actions instead."""
     n, S = cells.n, cells.S
     if not Zc.is_cuda:
-        with torch.no_grad():
-            a, lp, _ = cell_head_torch(_rows_cm(Zc, cells), mask_bits, None, generator)
-        return a, lp
+        return _sample_torch(_rows_cm(Zc, cells), mask_bits, generator, greedy)
     k = N.kernels()
     nc = n * S
     dev = Zc.device
@@ -340,8 +340,8 @@ def sample_rows(Zc: torch.Tensor, cells, mask_bits: torch.Tensor,
     N.check(k.mbk_masked_cell_rows_fwd(Zc.data_ptr(), Zc.shape[-1], cells.rowcell.data_ptr(),
                                        cells.totals.data_ptr(), nblk,
                                        mask_bits.contiguous().data_ptr(), action_out.data_ptr(),
-                                       rng_state.data_ptr(), 1, cell_logp.data_ptr(), None, st),
-            "masked_cell_rows_fwd")
+                                       rng_state.data_ptr(), 2 if greedy else 1,
+                                       cell_logp.data_ptr(), None, st), "masked_cell_rows_fwd")
     N.check(k.mbk_row_sum_rng(cell_logp.data_ptr(), n, S, logp_out.data_ptr(),
                               rng_state.data_ptr(), st), "row_sum_rng")
     return action_out, logp_out
@@ -356,12 +356,25 @@ def score(logits: torch.Tensor, mask_bits: torch.Tensor, action: torch.Tensor):
 
 
 def sample(logits: torch.Tensor, mask_bits: torch.Tensor, rng_state: torch.Tensor | None = None,
-           generator: torch.Generator | None = None):
-    """(action [N,S,7] uint8, logp [N]) sampled under the mask (no grad)."""
+           generator: torch.Generator | None = None, greedy: bool = False):
+    """(action [N,S,7] uint8, logp [N]) sampled under the mask (no grad); greedy: the arg-max
+    action of every segment (``greedy``) with its log-prob, no random numbers."""
     if logits.is_cuda:
-        return sample_gpu(logits, mask_bits.contiguous(), rng_state)
+        return sample_gpu(logits, mask_bits.contiguous(), rng_state, greedy=greedy)
+    return _sample_torch(logits, mask_bits, generator, greedy)
+
+
+def _sample_torch(logits, mask_bits, generator, greedy_mode: bool):
+    """CPU sampling: multinomial draws, or the arg-max actions scored by the torch formulation"""
     with torch.no_grad():
-        a, lp, _ = cell_head_torch(logits, mask_bits, None, generator)
+        if greedy_mode:
+            n = logits.shape[0]
+            bits = mask_bits if mask_bits.dtype != torch.bool else pack_mask(
+                mask_bits.view(n, -1, CELL))
+            a = greedy(logits, bits)
+            _, lp, _ = cell_head_torch(logits, mask_bits, a)
+        else:
+            a, lp, _ = cell_head_torch(logits, mask_bits, None, generator)
     return a, lp
 
 

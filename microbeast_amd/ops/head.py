@@ -78,9 +78,11 @@ class SparseHead:
 
     def sample_bucketed(self, X: torch.Tensor, mask_bits: torch.Tensor, action: torch.Tensor,
                         rng: torch.Tensor, logp_out: torch.Tensor,
-                        act16_out: torch.Tensor | None = None) -> torch.Tensor:
+                        act16_out: torch.Tensor | None = None,
+                        greedy: bool = False) -> torch.Tensor:
         """Sample with the buckets the decode kernel built this step (no sort: 3 launches).
-        act16_out: also pack the actions into the env's 16-bit codes in the last launch."""
+        act16_out: also pack the actions into the env's 16-bit codes in the last launch.
+        greedy: arg-max actions instead of sampled ones (the step counter still advances)."""
         F = X.shape[0]
         assert F == self._bucket_E
         k = N.kernels()
@@ -92,7 +94,8 @@ class SparseHead:
                                           mask_bits.data_ptr(), action.data_ptr(),
                                           rng.data_ptr(), self.bucket.data_ptr(),
                                           self.bucket_cnt.data_ptr(), F, self.S, self.fwd_grid,
-                                          self.cell_lp.data_ptr(), st), "head_fwd_counts")
+                                          self.cell_lp.data_ptr(), int(greedy), st),
+                    "head_fwd_counts")
             N.check(k.mbk_row_sum_pack(self.cell_lp.data_ptr(), F, self.S, logp_out.data_ptr(),
                                        rng.data_ptr(), action.data_ptr(), act16_out.data_ptr(),
                                        self.bucket_cnt.data_ptr(), self.S, st), "row_sum_pack")
@@ -101,8 +104,8 @@ class SparseHead:
                                  self.grp_count.data_ptr(), self.unit_cell.data_ptr(),
                                  self.unit_row.data_ptr(), self.totals.data_ptr(), st), "head_units")
         N.check(k.mbk_head_fwd(X.data_ptr(), self.Wp.data_ptr(), self.bp.data_ptr(),
-                               mask_bits.data_ptr(), action.data_ptr(), rng.data_ptr(), 1,
-                               self.bucket.data_ptr(), self.unit_cell.data_ptr(),
+                               mask_bits.data_ptr(), action.data_ptr(), rng.data_ptr(),
+                               2 if greedy else 1, self.bucket.data_ptr(), self.unit_cell.data_ptr(),
                                self.unit_row.data_ptr(), self.grp_start.data_ptr(),
                                self.grp_count.data_ptr(), self.totals.data_ptr(), self.S,
                                self.fwd_grid, self.cell_lp.data_ptr(), None, 0, st),
@@ -161,8 +164,11 @@ class SparseHead:
     def forward(self, X: torch.Tensor, mask_bits: torch.Tensor, action: torch.Tensor,
                 sample: bool, rng: torch.Tensor | None, logp_out: torch.Tensor | None = None,
                 ent_out: torch.Tensor | None = None, want_ent: bool = True,
-                abits: torch.Tensor | None = None):
-        """X bf16 [F,256] contiguous. sample=True writes ``action`` (uint8 [F,S,7])."""
+                abits: torch.Tensor | None = None, greedy: bool = False):
+        """X bf16 [F,256] contiguous. sample=True writes ``action`` (uint8 [F,S,7]): sampled,
+        or with greedy the arg-max of every segment (lowest legal index at the legal maximum;
+        no random numbers drawn, the step counter advances as for a sampled step)."""
+        assert sample or not greedy, "greedy is a mode of sampling"
         F = X.shape[0]
         k = N.kernels()
         st = N.stream_ptr()
@@ -202,7 +208,8 @@ class SparseHead:
         else:
             N.check(k.mbk_head_fwd(X.data_ptr(), self.Wp.data_ptr(), self.bp.data_ptr(),
                                    mask_bits.data_ptr(), action.data_ptr(), N.ptr(rng),
-                                   int(sample), self.pairs.data_ptr(), self.unit_cell.data_ptr(),
+                                   2 if greedy else int(sample), self.pairs.data_ptr(),
+                                   self.unit_cell.data_ptr(),
                                    self.unit_row.data_ptr(), self.grp_start.data_ptr(),
                                    self.grp_count.data_ptr(), self.totals.data_ptr(), self.S,
                                    self.fwd_grid, self.cell_lp.data_ptr(),
@@ -314,7 +321,8 @@ def sparse_score(X, W, b, mask_bits, action, head: SparseHead):
 
 @torch.no_grad()
 def sparse_sample(X, W, b, mask_bits, rng, head: SparseHead, action_out=None, logp_out=None,
-                  prepacked: bool = False, bucketed: bool = False, act16_out=None):
+                  prepacked: bool = False, bucketed: bool = False, act16_out=None,
+                  greedy: bool = False):
     F = X.shape[0]
     if action_out is None:
         action_out = torch.empty(F, head.S, 7, dtype=torch.uint8, device=X.device)
@@ -324,7 +332,8 @@ def sparse_sample(X, W, b, mask_bits, rng, head: SparseHead, action_out=None, lo
         if logp_out is None:
             logp_out = torch.empty(F, dtype=torch.float32, device=X.device)
         return action_out, head.sample_bucketed(X.contiguous(), mask_bits.contiguous(),
-                                                action_out, rng, logp_out, act16_out)
+                                                action_out, rng, logp_out, act16_out,
+                                                greedy=greedy)
     logp, _ = head.forward(X.contiguous(), mask_bits.contiguous(), action_out, sample=True,
-                           rng=rng, logp_out=logp_out, want_ent=False)
+                           rng=rng, logp_out=logp_out, want_ent=False, greedy=greedy)
     return action_out, logp

@@ -59,10 +59,12 @@ class EngineFailure(RuntimeError):
     process is intact and may rebuild the actor side (train.py)."""
 
 
-def graph_policy_step(io: dict, m, rng: torch.Tensor, E: int, size: int, device) -> None:
+def graph_policy_step(io: dict, m, rng: torch.Tensor, E: int, size: int, device,
+                      greedy: bool = False) -> None:
     """The captured graph's policy step (6 launches for the flat agent: decode + bucket, stage-0
     conv, trunk, network.5 + critic, head, finale) on fixed-address I/O ``io`` (``make_io``).
-    The fused two-launch step (ops/act.py) is pinned bit-identical to it."""
+    The fused two-launch step (ops/act.py) is pinned bit-identical to it. greedy: arg-max
+    actions instead of sampled ones (a captured graph has the mode baked in at capture)."""
     k = N.kernels()
     st = N.stream_ptr()
     # sparse-head models (flat IMPALA head) bucket their active pairs in the decode pass;
@@ -82,7 +84,7 @@ def graph_policy_step(io: dict, m, rng: torch.Tensor, E: int, size: int, device)
         _, _, value = m.act(io["in_obs"], io["in_mask"], rng, action_out=io["out_action"],
                             logp_out=io["out_logp"], bucketed=True,
                             logits_out=io.get("out_logits"), value_out=io["out_value"],
-                            act16_out=io["out_act16"])
+                            act16_out=io["out_act16"], greedy=greedy)
         packed = True
     else:
         N.check(k.mbk_decode_obs_mask(io["in_codes"].data_ptr(), io["in_res"].data_ptr(),
@@ -93,16 +95,19 @@ def graph_policy_step(io: dict, m, rng: torch.Tensor, E: int, size: int, device)
                 logits, value = m.policy_value_pbc(io["in_obs"])
                 io["out_logits"].copy_(pbc_to_cell_major(logits).reshape(io["out_logits"].shape))
                 cell_head.sample_pbc(logits, io["in_mask"], rng, action_out=io["out_action"],
-                                     cell_logp=io["cell_logp"], logp_out=io["out_logp"])
+                                     cell_logp=io["cell_logp"], logp_out=io["out_logp"],
+                                     greedy=greedy)
             else:                    # GridNet: active-cell logits straight into the sampler
                 _, _, value = m.act(io["in_obs"], io["in_mask"], rng, action_out=io["out_action"],
-                                    cell_logp=io["cell_logp"], logp_out=io["out_logp"])
+                                    cell_logp=io["cell_logp"], logp_out=io["out_logp"],
+                                    greedy=greedy)
         else:
             logits, value = m.policy_value(io["in_obs"])
             if "out_logits" in io:
                 io["out_logits"].copy_(logits.reshape(io["out_logits"].shape))
             cell_head.sample_gpu(logits, io["in_mask"], rng, action_out=io["out_action"],
-                                 cell_logp=io["cell_logp"], logp_out=io["out_logp"])
+                                 cell_logp=io["cell_logp"], logp_out=io["out_logp"],
+                                 greedy=greedy)
     if value.data_ptr() != io["out_value"].data_ptr():  # (written in place when fused)
         io["out_value"].copy_(value.view(-1))
     if not packed:
@@ -137,7 +142,7 @@ class GpuActorRuntime:
                  env_index_base: int = 0, selfplay_groups: int = 0, fp8_policy: bool = False,
                  n_lanes: int | None = None,
                  reference_keys: bool = False, policy_logits: bool = False,
-                 preroll: int = 0, fused_act: bool | None = None):
+                 preroll: int = 0, fused_act: bool | None = None, greedy: bool = False):
         """preroll > 1: every env first plays r ~ U[0, preroll) steps of the uniform
         random-init policy on the CPU (engine.h EngineConfig::preroll), so the run starts from
         envs spread over the game's phases rather than all at their first frame.
@@ -146,7 +151,9 @@ class GpuActorRuntime:
         78*h*w policy logits of every step (the sparse acting head never needs them, so
         this adds one dense head GEMM per policy step and 312*h*w bytes per frame).
         fused_act: None picks the fused acting step whenever ops/act.py supports the model
-        shape; False forces the captured-graph step (the tests compare the two)."""
+        shape; False forces the captured-graph step (the tests compare the two).
+        greedy: player 0 takes the arg-max action of every component instead of sampling
+        (checkpoint evaluation); the self-play opponent still samples."""
         rt = N.runtime()
         self.device = device
         self.size, self.S = size, size * size
@@ -185,6 +192,7 @@ class GpuActorRuntime:
         # the GPU, not the single stream, is the limit there, so the default is one lane
         self.n_lanes = max(1, min(n_groups, n_lanes if n_lanes is not None else 1))
         self.fp8_policy = fp8_policy
+        self.greedy = bool(greedy)
         self.selfplay_groups = int(selfplay_groups)
         self.lanes = []
         for ln in range(self.n_lanes):
@@ -197,7 +205,7 @@ class GpuActorRuntime:
                 lane["model"].fp8_inference = True
             lane["flat"] = FlatParams(lane["model"], dev)
             lane["pack_graph"] = self._capture_pack(lane["model"])
-            lane["graph"] = self._capture(lane["io"], lane["model"], lane["rng"])
+            lane["graph"] = self._capture(lane["io"], lane["model"], lane["rng"], self.greedy)
             if self.selfplay_groups > 0:
                 lane["io_p1"] = self._make_io()
                 lane["rng_p1"] = torch.tensor(
@@ -239,6 +247,7 @@ class GpuActorRuntime:
             bufs["lanes"].append(d)
         torch.cuda.synchronize()
         self.engine = rt.GpuEngine(cfg, bufs)
+        self.engine.set_greedy(self.greedy)
         # fused acting steps (ops/act.py): 2 launches per policy step that write the rollout
         # row in place, instead of the captured 6-launch graph + scatter copy. Headline agent
         # shape (16x16, bf16 trunk), self-play groups included (the opponent's step runs the
@@ -276,8 +285,8 @@ class GpuActorRuntime:
     def _make_io(self):
         return make_io(self.E, self.S, self.device, getattr(self, "emit_logits", False))
 
-    def _policy_step(self, io, m, rng):
-        graph_policy_step(io, m, rng, self.E, self.size, self.device)
+    def _policy_step(self, io, m, rng, greedy: bool = False):
+        graph_policy_step(io, m, rng, self.E, self.size, self.device, greedy)
 
     def _capture_pack(self, model):
         """Graph of ``model.pack_inference`` (derived weight buffers), replayed by the engine
@@ -296,17 +305,17 @@ class GpuActorRuntime:
         torch.cuda.synchronize()
         return g
 
-    def _capture(self, io, model, rng):
+    def _capture(self, io, model, rng, greedy: bool = False):
         s = torch.cuda.Stream(device=self.device)
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(3):  # warm up allocator / kernels outside capture
-                self._policy_step(io, model, rng)
+                self._policy_step(io, model, rng, greedy)
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, stream=s):
-            self._policy_step(io, model, rng)
+            self._policy_step(io, model, rng, greedy)
         torch.cuda.synchronize()
         rng[1] = 0
         return g
