@@ -53,6 +53,12 @@ class Flags:
     pg_rho_bar: float = 1.0
     reward_clip: float = 0.0
     max_grad_norm: float = 0.0
+    algo: str = "impala"          # impala (V-trace) | ppo (GAE + clipped surrogate, ops/ppo.py)
+    gae_lambda: float = 0.95      # ppo: GAE lambda
+    ppo_clip: float = 0.1         # ppo: ratio clip eps
+    ppo_value_clip: float = 0.1   # ppo: value clip eps_v (0 = unclipped value loss)
+    ppo_epochs: int = 1           # ppo: full-batch optimiser steps per rollout
+    ppo_norm_adv: bool = True     # ppo: normalise advantages over the rank's batch
     # --- environment
     env: str = "synthetic"        # synthetic | microrts (gym-microrts adapter, if installed)
     opponents: str = "coac,coac,coac,random_biased,light_rush,worker_rush"

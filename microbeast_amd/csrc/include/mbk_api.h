@@ -112,6 +112,23 @@ int mbk_codes_to_rows(const void* act16, int E, int S, uint32_t* rows, int strid
 int mbk_act_trunk(const MbkActModel* m, const MbkActStep* s, hipStream_t stream);
 int mbk_act_head(const MbkActModel* m, const MbkActStep* s, hipStream_t stream);
 
+// ---- PPO objective (ppo.hip) ----------------------------------------------------------------
+// Time-major fp32 [T, B] arrays (v_old / values / g_value: [T+1, B], row T = the bootstrap).
+// GAE(lambda) from one value snapshot: adv, ret [T, B] and stats = (mean, 1 / (std + 1e-8)) of
+// adv over its T*B elements, (0, 1) when norm_adv == 0. partials: 3 * ceil(B / 256) floats.
+int mbk_gae(const float* v_old, const float* reward, const uint8_t* done, int T, int B,
+            float gamma, float lambda, float reward_clip, int norm_adv, float* adv, float* ret,
+            float* partials, float* stats, hipStream_t stream);
+// Clipped surrogate + clipped value loss and their gradients g_logp [T, B], g_value [T+1, B]
+// (row T zeroed); losses[7] = pg, value, entropy, total, mean ratio, approx_kl, clip_frac.
+// clip_lo / clip_hi = 1 -/+ clip as the caller rounds them; value_clip 0 = unclipped value
+// loss; entropy may be null. partials: 6 * ceil((T+1) * B / 256) floats.
+int mbk_ppo_loss(const float* logp_new, const float* logp_old, const float* values,
+                 const float* v_old, const float* adv, const float* ret, const float* entropy,
+                 const float* stats, int T, int B, float clip_lo, float clip_hi, float clip,
+                 float value_clip, float baseline_cost, float entropy_cost, float* g_logp,
+                 float* g_value, float* partials, float* losses, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,285 @@
+// PPO objective (Schulman et al. 2017): GAE(lambda) advantages + the clipped surrogate and
+// clipped value losses with their gradients, beside the V-trace path (vtrace.hip).
+//
+// Reference: libs/utils.py:104-163 (get_deltas / get_advantages: dead code there) and the name
+// of its learn step (PPO_learn, which is V-trace). Two launchers, called once per rollout and
+// once per epoch:
+//
+//   mbk_gae       v_old [T+1,B], reward, done [T,B] -> adv, ret [T,B], stats[2]
+//     delta_t = r_t + gamma nd_t v_old[t+1] - v_old[t],  A_t = delta_t + gamma lambda nd_t A_{t+1}
+//     (A_T = 0),  R_t = A_t + v_old[t];  stats = (mean A, 1 / (std A + 1e-8)) over the T*B
+//     elements (population std), or (0, 1) with normalisation off.
+//   mbk_ppo_loss  logp_new, logp_old, v, v_old, adv, ret, entropy, stats -> g_logp [T,B],
+//     g_value [T+1,B] (row T = 0), losses[7]
+//     A^ = (A - mean) rstd, ratio = exp(logp_new - logp_old), M = T*B
+//     pg    = -mean(min(ratio A^, clamp(ratio, 1-eps, 1+eps) A^))
+//     value = bc mean(max((v-R)^2, (v_c-R)^2)),  v_c = v_old + clamp(v - v_old, -eps_v, eps_v)
+//             (eps_v = 0: the plain (v-R)^2)
+//     dL/dlogp = -A^ ratio / M, or 0 where (A^ > 0, ratio > 1+eps) or (A^ < 0, ratio < 1-eps)
+//     dL/dv    = 2 bc (v-R)/M where (v-R)^2 >= (v_c-R)^2; else 2 bc (v_c-R)/M where
+//                |v - v_old| <= eps_v; else 0
+//     dL/dH    = -entropy_cost / M (constant: the caller's seed)
+//     losses   = pg, value, entropy, total, mean ratio, approx_kl = mean((ratio-1) - log ratio),
+//                clip_frac = mean(|ratio-1| > eps)
+//
+// Every reduction is two-pass and ordered (per-block partials, one finalize wave): no float
+// atomics, bit-reproducible between runs. The advantage statistics merge per-block
+// (n, mean, M2) triples (Chan et al.), not a global sum of squares.
+#include "../include/mbk_api.h"
+#include "common.h"
+
+using namespace mbk;
+
+namespace {
+
+// (n, mean, M2) of a set; merge of two disjoint sets (Chan, Golub, LeVeque 1979)
+struct Moments {
+  float n, mean, m2;
+};
+__device__ __forceinline__ Moments merge(Moments a, Moments b) {
+  const float n = a.n + b.n;
+  if (n == 0.f) return a;
+  const float d = b.mean - a.mean, f = b.n / n;
+  return {n, a.mean + d * f, a.m2 + b.m2 + d * d * a.n * f};
+}
+// lane 0 ends with the wave's merge, in a fixed order
+__device__ __forceinline__ Moments wave_merge(Moments m) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    Moments r;
+    r.n = __shfl_down(m.n, o, 64);
+    r.mean = __shfl_down(m.mean, o, 64);
+    r.m2 = __shfl_down(m.m2, o, 64);
+    m = merge(m, r);
+  }
+  return m;
+}
+
+__global__ __launch_bounds__(256) void gae_kernel(
+    const float* __restrict__ v_old, const float* __restrict__ reward,
+    const uint8_t* __restrict__ done, int T, int B, float gamma, float lambda, float reward_clip,
+    float* __restrict__ adv_out, float* __restrict__ ret_out,
+    float* __restrict__ partials /* [gridDim.x][3] */) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  Moments mo = {0.f, 0.f, 0.f};
+  if (b < B) {
+    float v_next = v_old[(size_t)T * B + b];
+    float acc = 0.f;
+    for (int t = T - 1; t >= 0; --t) {
+      const size_t i = (size_t)t * B + b;
+      float r = reward[i];
+      if (reward_clip > 0.f) r = fmaxf(-reward_clip, fminf(reward_clip, r));
+      const float disc = done[i] ? 0.f : gamma;
+      const float v = v_old[i];
+      const float delta = r + disc * v_next - v;
+      acc = delta + disc * lambda * acc;
+      adv_out[i] = acc;
+      ret_out[i] = acc + v;
+      // Welford update of the lane's own column
+      mo.n += 1.f;
+      const float d = acc - mo.mean;
+      mo.mean += d / mo.n;
+      mo.m2 += d * (acc - mo.mean);
+      v_next = v;
+    }
+  }
+  __shared__ Moments red[4];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  mo = wave_merge(mo);
+  if (lane == 0) red[wave] = mo;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    Moments s = red[0];
+    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) s = merge(s, red[w]);
+    partials[blockIdx.x * 3 + 0] = s.n;
+    partials[blockIdx.x * 3 + 1] = s.mean;
+    partials[blockIdx.x * 3 + 2] = s.m2;
+  }
+}
+
+// stats[0..1] = mean, 1 / (std + 1e-8); (0, 1) with normalisation off
+__global__ __launch_bounds__(64) void gae_finalize_kernel(const float* __restrict__ partials,
+                                                          int nblocks, int norm,
+                                                          float* __restrict__ stats) {
+  const int lane = threadIdx.x;
+  Moments s = {0.f, 0.f, 0.f};
+  for (int i = lane; i < nblocks; i += 64)
+    s = merge(s, Moments{partials[i * 3], partials[i * 3 + 1], partials[i * 3 + 2]});
+  s = wave_merge(s);
+  if (lane == 0) {
+    const float sd = sqrtf(fmaxf(s.m2, 0.f) / fmaxf(s.n, 1.f));
+    stats[0] = norm ? s.mean : 0.f;
+    stats[1] = norm ? 1.f / (sd + 1e-8f) : 1.f;
+  }
+}
+
+constexpr int kSums = 6;  // surrogate, value, entropy, ratio, kl, clipped count
+
+struct PpoParams {
+  float mean, rstd, lo, hi, clip, vclip, bc2_invM, invM;
+};
+
+// one element: gradients out, sums accumulated
+__device__ __forceinline__ void ppo_element(float lpn, float lpo, float v, float vo, float adv,
+                                            float ret, float ent, const PpoParams& p,
+                                            float& g_logp, float& g_value, float s[kSums]) {
+  const float lr = lpn - lpo;
+  const float ratio = __expf(lr);
+  const float a = (adv - p.mean) * p.rstd;
+  const float s1 = ratio * a;
+  const float s2 = fminf(fmaxf(ratio, p.lo), p.hi) * a;
+  const bool out = (a > 0.f && ratio > p.hi) || (a < 0.f && ratio < p.lo);
+  g_logp = out ? 0.f : -s1 * p.invM;
+  const float e = v - ret, e1 = e * e;
+  float vterm = e1, gv = e;
+  // inside the clip range v_c = v: the first case. Outside it v_c = v_old +- eps_v is constant
+  // in v, so where its error is the larger one the gradient is 0
+  const float d = v - vo;
+  if (p.vclip > 0.f && fabsf(d) > p.vclip) {
+    const float ec = vo + copysignf(p.vclip, d) - ret, e2 = ec * ec;
+    if (e1 < e2) {
+      vterm = e2;
+      gv = 0.f;
+    }
+  }
+  g_value = p.bc2_invM * gv;
+  s[0] += fminf(s1, s2);
+  s[1] += vterm;
+  s[2] += ent;
+  s[3] += ratio;
+  s[4] += (ratio - 1.f) - lr;
+  s[5] += fabsf(ratio - 1.f) > p.clip ? 1.f : 0.f;
+}
+
+// VEC = 4: 128-bit loads / stores (B % 4 == 0 and 16-byte aligned arrays); VEC = 1: scalar.
+// Items [0, M / VEC) are the T*B elements; items up to (M + B) / VEC zero g_value's row T.
+template <int VEC>
+__global__ __launch_bounds__(256) void ppo_loss_kernel(
+    const float* __restrict__ logp_new, const float* __restrict__ logp_old,
+    const float* __restrict__ values, const float* __restrict__ v_old,
+    const float* __restrict__ adv, const float* __restrict__ ret,
+    const float* __restrict__ entropy, const float* __restrict__ stats, size_t M, size_t MB,
+    float lo, float hi, float clip, float vclip, float baseline_cost,
+    float* __restrict__ g_logp, float* __restrict__ g_value,
+    float* __restrict__ partials /* [gridDim.x][kSums] */) {
+  const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * VEC;
+  float s[kSums] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (i < M) {
+    PpoParams p;
+    p.mean = stats[0];
+    p.rstd = stats[1];
+    p.lo = lo;
+    p.hi = hi;
+    p.clip = clip;
+    p.vclip = vclip;
+    p.invM = 1.f / (float)M;
+    p.bc2_invM = 2.f * baseline_cost * p.invM;
+    if constexpr (VEC == 4) {
+      const float4 a = *(const float4*)(logp_new + i), b = *(const float4*)(logp_old + i);
+      const float4 c = *(const float4*)(values + i), d = *(const float4*)(v_old + i);
+      const float4 e = *(const float4*)(adv + i), f = *(const float4*)(ret + i);
+      float4 h = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (entropy) h = *(const float4*)(entropy + i);
+      float4 gl, gv;
+      ppo_element(a.x, b.x, c.x, d.x, e.x, f.x, h.x, p, gl.x, gv.x, s);
+      ppo_element(a.y, b.y, c.y, d.y, e.y, f.y, h.y, p, gl.y, gv.y, s);
+      ppo_element(a.z, b.z, c.z, d.z, e.z, f.z, h.z, p, gl.z, gv.z, s);
+      ppo_element(a.w, b.w, c.w, d.w, e.w, f.w, h.w, p, gl.w, gv.w, s);
+      *(float4*)(g_logp + i) = gl;
+      *(float4*)(g_value + i) = gv;
+    } else {
+      float gl, gv;
+      ppo_element(logp_new[i], logp_old[i], values[i], v_old[i], adv[i], ret[i],
+                  entropy ? entropy[i] : 0.f, p, gl, gv, s);
+      g_logp[i] = gl;
+      g_value[i] = gv;
+    }
+  } else if (i < MB) {  // the bootstrap row has no gradient
+    if constexpr (VEC == 4) {
+      *(float4*)(g_value + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+      g_value[i] = 0.f;
+    }
+  }
+  __shared__ float red[4][kSums];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+  for (int k = 0; k < kSums; ++k) {
+    const float w = wave_sum(s[k]);
+    if (lane == 0) red[wave][k] = w;
+  }
+  __syncthreads();
+  if (threadIdx.x < kSums) {
+    float t = 0.f;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += red[w][threadIdx.x];
+    partials[(size_t)blockIdx.x * kSums + threadIdx.x] = t;
+  }
+}
+
+// losses[0..6] = pg, value, entropy, total, mean ratio, approx_kl, clip_frac
+__global__ __launch_bounds__(64) void ppo_finalize_kernel(const float* __restrict__ partials,
+                                                          int nblocks, size_t M,
+                                                          float baseline_cost, float entropy_cost,
+                                                          float* __restrict__ losses) {
+  const int lane = threadIdx.x;
+  float s[kSums] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int i = lane; i < nblocks; i += 64)
+    for (int k = 0; k < kSums; ++k) s[k] += partials[(size_t)i * kSums + k];
+  for (int k = 0; k < kSums; ++k) s[k] = wave_sum(s[k]);
+  if (lane == 0) {
+    const float invM = 1.f / (float)M;
+    const float pg = -s[0] * invM, vl = baseline_cost * s[1] * invM, ent = s[2] * invM;
+    losses[0] = pg;
+    losses[1] = vl;
+    losses[2] = ent;
+    losses[3] = pg + vl - entropy_cost * ent;
+    losses[4] = s[3] * invM;
+    losses[5] = s[4] * invM;
+    losses[6] = s[5] * invM;
+  }
+}
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+}  // namespace
+
+extern "C" int mbk_gae(const float* v_old, const float* reward, const uint8_t* done, int T, int B,
+                       float gamma, float lambda, float reward_clip, int norm_adv, float* adv,
+                       float* ret, float* partials, float* stats, hipStream_t stream) {
+  if (T < 1 || B < 1) return (int)hipErrorInvalidValue;
+  const int nb = (B + 255) / 256;
+  hipLaunchKernelGGL(gae_kernel, dim3(nb), dim3(256), 0, stream, v_old, reward, done, T, B, gamma,
+                     lambda, reward_clip, adv, ret, partials);
+  hipLaunchKernelGGL(gae_finalize_kernel, dim3(1), dim3(64), 0, stream, partials, nb, norm_adv,
+                     stats);
+  return (int)hipGetLastError();
+}
+
+// partials: 6 * ceil((T+1) * B / 256) floats (the scalar kernel's blocks; the vector kernel
+// uses a quarter of them)
+extern "C" int mbk_ppo_loss(const float* logp_new, const float* logp_old, const float* values,
+                            const float* v_old, const float* adv, const float* ret,
+                            const float* entropy, const float* stats, int T, int B,
+                            float clip_lo, float clip_hi, float clip, float value_clip,
+                            float baseline_cost, float entropy_cost, float* g_logp,
+                            float* g_value, float* partials, float* losses, hipStream_t stream) {
+  if (T < 1 || B < 1) return (int)hipErrorInvalidValue;
+  const size_t M = (size_t)T * B, MB = M + (size_t)B;
+  const bool vec = B % 4 == 0 && aligned16(logp_new) && aligned16(logp_old) &&
+                   aligned16(values) && aligned16(v_old) && aligned16(adv) && aligned16(ret) &&
+                   (!entropy || aligned16(entropy)) && aligned16(g_logp) && aligned16(g_value);
+  const size_t items = vec ? MB / 4 : MB;
+  const size_t nb = (items + 255) / 256;
+  if (nb > 0x7fffffffull) return (int)hipErrorInvalidValue;
+  if (vec)
+    hipLaunchKernelGGL(ppo_loss_kernel<4>, dim3((unsigned)nb), dim3(256), 0, stream, logp_new,
+                       logp_old, values, v_old, adv, ret, entropy, stats, M, MB, clip_lo, clip_hi,
+                       clip, value_clip, baseline_cost, g_logp, g_value, partials);
+  else
+    hipLaunchKernelGGL(ppo_loss_kernel<1>, dim3((unsigned)nb), dim3(256), 0, stream, logp_new,
+                       logp_old, values, v_old, adv, ret, entropy, stats, M, MB, clip_lo, clip_hi,
+                       clip, value_clip, baseline_cost, g_logp, g_value, partials);
+  hipLaunchKernelGGL(ppo_finalize_kernel, dim3(1), dim3(64), 0, stream, partials, (int)nb, M,
+                     baseline_cost, entropy_cost, losses);
+  return (int)hipGetLastError();
+}

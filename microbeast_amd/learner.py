@@ -1,4 +1,5 @@
-"""IMPALA learner step: forward -> V-trace -> backward -> all-reduce -> Adam.
+"""IMPALA learner step: forward -> V-trace -> backward -> all-reduce -> Adam (``algo="ppo"``:
+the PPO objective in its place, ``Learner._learn_ppo``).
 
 Reference: ``PPO_learn`` (libs/utils.py:223-342) + the learner loop
 (microbeast.py:211-248). Re-designed:
@@ -22,6 +23,7 @@ import torch
 
 from .ops.copy import full
 from .ops.optim import FlatAdam, FlatParams
+from .ops.ppo import gae, ppo_loss
 from .ops.vtrace import VTraceWorkspace, vtrace
 from .parallel.dist import DistInfo, GradAllReducer, broadcast_flat
 from .utils.metrics import PhaseTimer
@@ -42,6 +44,18 @@ class LearnerHParams:
     bucket_mb: float = 8.0
     allreduce_dtype: str = "fp32"  # fp32 | bf16 (gradient all-reduce payload)
     comm_rehearsal: bool = False   # world 1: stand-in collectives on a 4th stream (dist.py)
+    algo: str = "impala"           # impala (V-trace) | ppo (ops/ppo.py)
+    gae_lambda: float = 0.95       # ppo: GAE lambda
+    ppo_clip: float = 0.1          # ppo: ratio clip eps
+    ppo_value_clip: float = 0.1    # ppo: value clip eps_v (0: unclipped value loss)
+    ppo_epochs: int = 1            # ppo: full-batch optimiser steps per rollout
+    ppo_norm_adv: bool = True      # ppo: normalise the advantages over the rank's batch
+
+    def __post_init__(self):
+        if self.algo not in ("impala", "ppo"):
+            raise ValueError(f"--algo {self.algo!r}: expected impala | ppo")
+        if self.ppo_epochs < 1:
+            raise ValueError(f"--ppo_epochs {self.ppo_epochs}: expected >= 1")
 
 
 class Learner:
@@ -68,7 +82,10 @@ class Learner:
     def learn(self, batch: dict, sync_timing: bool = False) -> torch.Tensor:
         """batch keys (time-major): obs [T+1,B,...], mask [T+1,B,S,3] int32,
         action [T+1,B,S,7] uint8, logp [T+1,B], reward [T+1,B], done [T+1,B].
-        Returns the device tensor [5] = pg, value, entropy, total, mean rho."""
+        Returns the device tensor [5] = pg, value, entropy, total, mean rho (``algo="ppo"``:
+        [7], see ``_learn_ppo``)."""
+        if self.hp.algo == "ppo":
+            return self._learn_ppo(batch, sync_timing)
         t0 = time.perf_counter()
         self.phases.start()
         obs, mask, action = batch["obs"], batch["mask"], batch["action"]
@@ -115,6 +132,74 @@ class Learner:
         self.n_updates += 1
         self.timing = {"fwd_s": t1 - t0, "bwd_allreduce_s": t2 - t1, "optim_s": t3 - t2}
         return vt.losses
+
+    def _learn_ppo(self, batch: dict, sync_timing: bool = False) -> torch.Tensor:
+        """``ppo_epochs`` full-batch epochs on one rollout: each is zero grads -> forward ->
+        clipped losses -> backward -> all-reduce -> Adam, so Adam's step count advances once
+        per epoch while ``n_updates`` counts rollouts. Epoch 0 snapshots its own values as
+        ``v_old`` and runs GAE on them (ops/ppo.py); later epochs reuse adv / ret / stats /
+        v_old from the workspace. Under data parallelism the advantages are normalised with
+        each rank's own statistics. Returns the last epoch's device tensor [7] = pg, value,
+        entropy, total, mean ratio, approx_kl, clip_frac; nothing syncs the host."""
+        hp = self.hp
+        t_fwd = t_bwd = t_opt = 0.0
+        self.phases.start()
+        obs, mask, action = batch["obs"], batch["mask"], batch["action"]
+        T1, B = batch["logp"].shape[:2]
+        T = T1 - 1
+        flat_obs = obs.reshape(T1 * B, *obs.shape[2:])
+        S = mask.shape[2]
+        m = mask[:T].reshape(T * B, S, mask.shape[-1])
+        a = action[:T].reshape(T * B, S, action.shape[-1])
+        kw = {}
+        ab = batch.get("abits")
+        if ab is not None and getattr(self.model, "accepts_abits", False):
+            kw["abits"] = ab[:T].reshape(T * B, ab.shape[-1])
+        cuda = batch["logp"].is_cuda
+        g = v_old = None
+        for epoch in range(hp.ppo_epochs):
+            t0 = time.perf_counter()
+            self.flat.zero_grad()
+            self.reducer.start_step()
+            logp, ent, value = self.model.evaluate(flat_obs, m, a, n_score=T * B, **kw)
+            if epoch == 0:
+                if cuda:  # (a workspace buffer: the forward's own output is rewritten per epoch)
+                    v_old = self.ws.get("ppo_v_old", (T1, B), value.device)
+                    v_old.copy_(value.detach().view(T1, B))
+                else:
+                    v_old = value.detach().float().view(T1, B).clone()
+                g = gae(v_old, batch["reward"][:T], batch["done"][:T], gamma=hp.gamma,
+                        lam=hp.gae_lambda, reward_clip=hp.reward_clip, norm_adv=hp.ppo_norm_adv,
+                        ws=self.ws)
+            out = ppo_loss(logp.view(T, B), batch["logp"][:T], value.view(T1, B), v_old, g.adv,
+                           g.ret, g.stats, ent.view(T, B), clip=hp.ppo_clip,
+                           value_clip=hp.ppo_value_clip, baseline_cost=hp.baseline_cost,
+                           entropy_cost=hp.entropy_cost, ws=self.ws)
+            self.phases.mark("fwd")
+            if sync_timing and cuda:
+                torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            torch.autograd.backward(
+                [logp, value, ent], [out.g_logp.reshape(-1), out.g_value.reshape(-1),
+                                     self._const_grad(ent, out.g_ent)])
+            if self.flat.adopt_grads() and self.info.enabled:
+                raise RuntimeError("a direct-gradient parameter's gradient was not written into "
+                                   "its flat slot; its all-reduce bucket went out stale")
+            self.phases.mark("bwd")
+            self.reducer.finish()
+            self.phases.mark("allreduce")
+            if sync_timing and cuda:
+                torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            self.opt.step(grad_scale=self.reducer.grad_scale)
+            self.phases.mark("optim")
+            if sync_timing and cuda:
+                torch.cuda.synchronize()
+            t3 = time.perf_counter()
+            t_fwd, t_bwd, t_opt = t_fwd + t1 - t0, t_bwd + t2 - t1, t_opt + t3 - t2
+        self.n_updates += 1
+        self.timing = {"fwd_s": t_fwd, "bwd_allreduce_s": t_bwd, "optim_s": t_opt}
+        return out.losses
 
     def _const_grad(self, like: torch.Tensor, value: float) -> torch.Tensor:
         """constant seed gradient (entropy term), filled once per shape / value"""

@@ -1,0 +1,184 @@
+"""PPO objective: GAE(lambda) advantages + clipped surrogate / clipped value losses and
+their gradients, beside V-trace (``ops/vtrace.py``).
+
+Reference: the learn step is called ``PPO_learn`` (libs/utils.py:277-329) but is IMPALA
+V-trace, and its advantage helpers (``get_deltas`` / ``get_advantages``,
+libs/utils.py:104-163; here ``ops/advantages.py``) are never called (C13). This is the
+working PPO path (Schulman et al. 2017).
+
+Inputs are time-major like V-trace's: ``logp_new / logp_old / reward / done / entropy``
+``[T, B]``, values ``[T+1, B]``; ``M = T * B``, ``nd_t = 1 - done_t``.
+
+``gae`` runs once per rollout on ``v_old``, a detached snapshot of the values the LEARNER
+computes in the rollout's first epoch -- not the behaviour values the actors stored: the
+engine never writes the behaviour value of a slot's bootstrap row T (it closes only obs, mask
+and the active-cell bitmap into the previous slot; the mono runtime stores its values under
+another key, ``baseline``). The learner's own epoch-0 values need no engine work and behave the
+same on both runtimes.
+
+    delta_t = r_t + gamma nd_t v_old[t+1] - v_old[t]
+    A_t     = delta_t + gamma lambda nd_t A_{t+1},  A_T = 0
+    R_t     = A_t + v_old[t]
+    stats   = (mean A, 1 / (std A + 1e-8))   population std over the M elements; (0, 1) with
+              ``norm_adv`` off. Under data parallelism each rank normalises with its own
+              batch's statistics (no collective).
+
+``ppo_loss`` runs once per epoch, with ``A^ = (A - stats[0]) * stats[1]`` and
+``ratio = exp(logp_new - logp_old)``:
+
+    pg       = -mean(min(ratio A^, clamp(ratio, 1-eps, 1+eps) A^))
+    value    = baseline_cost mean(max((v-R)^2, (v_c-R)^2)),
+               v_c = v_old + clamp(v - v_old, -eps_v, eps_v)   (eps_v = 0: plain (v-R)^2)
+    dL/dlogp = -A^ ratio / M, or 0 where (A^ > 0 and ratio > 1+eps) or (A^ < 0 and ratio < 1-eps)
+    dL/dv    = 2 bc (v-R)/M where (v-R)^2 >= (v_c-R)^2; else 2 bc (v_c-R)/M where
+               |v - v_old| <= eps_v; else 0.  Row T of g_value is 0. (Inside the clip range
+               v_c = v, so the middle case is the first one: the code tests |v - v_old| > eps_v
+               and does not compare two roundings of the same error.)
+    dL/dH    = -entropy_cost / M
+    losses   = [pg, value, entropy, total = pg + value - entropy_cost entropy, mean ratio,
+                approx_kl = mean((ratio-1) - log ratio), clip_frac = mean(|ratio-1| > eps)]
+
+Device tensors run the HIP kernels (``ppo.hip``: a one-lane-per-column reverse scan with
+per-block (n, mean, M2) partials, and one vectorised elementwise pass); a missing kernel is an
+error. CPU tensors run the same maths in fp32 torch ops (``gae_torch`` / ``ppo_loss_torch``:
+the test oracle, and what the mono runtime's CPU learner runs).
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import torch
+
+from .. import _native as N
+from .vtrace import VTraceWorkspace
+
+
+@dataclass
+class GaeOut:
+    adv: torch.Tensor    # [T, B] unnormalised advantages
+    ret: torch.Tensor    # [T, B] value targets adv + v_old[:T]
+    stats: torch.Tensor  # [2] mean, 1 / (std + 1e-8) of adv ((0, 1): normalisation off)
+
+
+@dataclass
+class PPOOut:
+    g_logp: torch.Tensor   # [T, B] dL/dlogp
+    g_value: torch.Tensor  # [T+1, B] dL/dV (row T = 0: bootstrap has no gradient)
+    g_ent: float           # dL/dentropy per frame (constant)
+    losses: torch.Tensor   # [7] pg, value, entropy, total, mean ratio, approx_kl, clip_frac
+    adv: torch.Tensor | None = None
+    ret: torch.Tensor | None = None
+
+
+def _f(x):
+    """fp32 compute; float64 inputs stay float64 (the tests' high-precision runs)"""
+    return x.detach() if x.dtype == torch.float64 else x.detach().float()
+
+
+def gae_torch(v_old, reward, done, gamma=0.99, lam=0.95, reward_clip=0.0,
+              norm_adv=True) -> GaeOut:
+    T, B = reward.shape
+    v = _f(v_old)
+    r = reward.to(v.dtype)
+    if reward_clip > 0:
+        r = r.clamp(-reward_clip, reward_clip)
+    disc = (~done.bool()).to(v.dtype) * gamma
+    delta = r + disc * v[1:T + 1] - v[:T]
+    acc = torch.zeros(B, dtype=v.dtype, device=v.device)
+    adv = torch.empty_like(delta)
+    for t in range(T - 1, -1, -1):
+        acc = delta[t] + disc[t] * lam * acc
+        adv[t] = acc
+    if norm_adv:
+        stats = torch.stack([adv.mean(), 1.0 / (adv.std(unbiased=False) + 1e-8)])
+    else:
+        stats = torch.tensor([0.0, 1.0], dtype=v.dtype, device=v.device)
+    return GaeOut(adv, adv + v[:T], stats)
+
+
+def ppo_loss_torch(logp_new, logp_old, values, v_old, adv, ret, stats, entropy=None, clip=0.1,
+                   value_clip=0.1, baseline_cost=0.5, entropy_cost=0.01) -> PPOOut:
+    T, B = logp_new.shape
+    M = float(T * B)
+    lpn = _f(logp_new)
+    dt = lpn.dtype
+    lr = lpn - logp_old.to(dt)
+    ratio = torch.exp(lr)
+    a = (adv.to(dt) - stats[0].to(dt)) * stats[1].to(dt)
+    lo, hi = 1.0 - clip, 1.0 + clip
+    s1, s2 = ratio * a, ratio.clamp(lo, hi) * a
+    out = ((a > 0) & (ratio > hi)) | ((a < 0) & (ratio < lo))
+    g_logp = torch.where(out, torch.zeros_like(s1), -s1 / M)
+    v_all = values.detach().to(dt)
+    v, vo, R = v_all[:T], v_old.to(dt)[:T], ret.to(dt)
+    e = v - R
+    e1 = e * e
+    vterm, gv = e1, e
+    if value_clip > 0:
+        # inside the clip range v_c = v (the first case); outside it v_c = v_old +- eps_v is
+        # constant in v, so where its error is the larger one the gradient is 0
+        d = v - vo
+        ec = vo + d.clamp(-value_clip, value_clip) - R
+        e2 = ec * ec
+        alt = (d.abs() > value_clip) & (e1 < e2)
+        vterm = torch.where(alt, e2, e1)
+        gv = torch.where(alt, torch.zeros_like(e), e)
+    g_value = torch.zeros_like(v_all)
+    g_value[:T] = 2.0 * baseline_cost * gv / M
+    pg = -torch.minimum(s1, s2).sum() / M
+    vl = baseline_cost * vterm.sum() / M
+    ent = (entropy.detach().to(dt).sum() / M if entropy is not None
+           else torch.zeros((), dtype=dt, device=ratio.device))
+    losses = torch.stack([pg, vl, ent, pg + vl - entropy_cost * ent, ratio.mean(),
+                          ((ratio - 1.0) - lr).mean(),
+                          ((ratio - 1.0).abs() > clip).to(dt).mean()])
+    return PPOOut(g_logp, g_value, -entropy_cost / M, losses, adv, ret)
+
+
+def gae(v_old, reward, done, gamma=0.99, lam=0.95, reward_clip=0.0, norm_adv=True,
+        ws: VTraceWorkspace | None = None) -> GaeOut:
+    """v_old: [T+1, B]; reward / done: [T, B]. The outputs live in ``ws`` (reused by the next
+    call with the same shape)."""
+    if not v_old.is_cuda:
+        return gae_torch(v_old, reward, done, gamma, lam, reward_clip, norm_adv)
+    T, B = reward.shape
+    dev = v_old.device
+    ws = ws or VTraceWorkspace()
+    adv = ws.get("ppo_adv", (T, B), dev)
+    ret = ws.get("ppo_ret", (T, B), dev)
+    partials = ws.get("ppo_gae_partials", (((B + 255) // 256) * 3,), dev)
+    stats = ws.get("ppo_stats", (2,), dev)
+    vo = v_old.detach().float().contiguous()
+    rew = reward.float().contiguous()
+    dn = done.to(torch.uint8).contiguous()
+    N.check(N.kernels().mbk_gae(vo.data_ptr(), rew.data_ptr(), dn.data_ptr(), T, B, gamma, lam,
+                                reward_clip, int(bool(norm_adv)), adv.data_ptr(), ret.data_ptr(),
+                                partials.data_ptr(), stats.data_ptr(), N.stream_ptr()), "gae")
+    return GaeOut(adv, ret, stats)
+
+
+def ppo_loss(logp_new, logp_old, values, v_old, adv, ret, stats, entropy=None, clip=0.1,
+             value_clip=0.1, baseline_cost=0.5, entropy_cost=0.01,
+             ws: VTraceWorkspace | None = None) -> PPOOut:
+    """logp_new / logp_old / adv / ret / entropy: [T, B]; values / v_old: [T+1, B]; stats: [2]
+    (``gae``'s)."""
+    if not logp_new.is_cuda:
+        return ppo_loss_torch(logp_new, logp_old, values, v_old, adv, ret, stats, entropy, clip,
+                              value_clip, baseline_cost, entropy_cost)
+    T, B = logp_new.shape
+    dev = logp_new.device
+    ws = ws or VTraceWorkspace()
+    g_logp = ws.get("ppo_g_logp", (T, B), dev)
+    g_value = ws.get("ppo_g_value", (T + 1, B), dev)
+    partials = ws.get("ppo_partials", ((((T + 1) * B + 255) // 256) * 6,), dev)
+    losses = ws.get("ppo_losses", (7,), dev)
+    c = lambda x: x.detach().float().contiguous()  # noqa: E731
+    lpn, lpo, val, vo, ad, rt, st = (c(logp_new), c(logp_old), c(values), c(v_old), c(adv),
+                                     c(ret), c(stats))
+    ent = c(entropy) if entropy is not None else None
+    N.check(N.kernels().mbk_ppo_loss(
+        lpn.data_ptr(), lpo.data_ptr(), val.data_ptr(), vo.data_ptr(), ad.data_ptr(),
+        rt.data_ptr(), N.ptr(ent), st.data_ptr(), T, B, 1.0 - clip, 1.0 + clip, clip, value_clip,
+        baseline_cost, entropy_cost, g_logp.data_ptr(), g_value.data_ptr(), partials.data_ptr(),
+        losses.data_ptr(), N.stream_ptr()), "ppo_loss")
+    return PPOOut(g_logp, g_value, -entropy_cost / float(T * B), losses, adv, ret)

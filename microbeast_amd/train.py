@@ -29,7 +29,7 @@ from .models.factory import make_model
 from .parallel import dist as D
 from .utils.checkpoint import (load_checkpoint, load_league_shard, restore, save_checkpoint,
                                save_league_shard)
-from .utils.metrics import CsvLogger
+from .utils.metrics import PPO_LOSS_COLUMNS, CsvLogger
 
 
 def scaled_lr(flags: Flags, frames_per_update: int) -> float:
@@ -57,7 +57,10 @@ def _hparams(flags: Flags, lr: float | None = None) -> LearnerHParams:
                           baseline_cost=flags.baseline_cost, entropy_cost=flags.entropy_cost,
                           rho_bar=flags.rho_bar, c_bar=flags.c_bar, pg_rho_bar=flags.pg_rho_bar,
                           reward_clip=flags.reward_clip, max_grad_norm=flags.max_grad_norm,
-                          bucket_mb=flags.bucket_mb, allreduce_dtype=flags.allreduce_dtype)
+                          bucket_mb=flags.bucket_mb, allreduce_dtype=flags.allreduce_dtype,
+                          algo=flags.algo, gae_lambda=flags.gae_lambda, ppo_clip=flags.ppo_clip,
+                          ppo_value_clip=flags.ppo_value_clip, ppo_epochs=flags.ppo_epochs,
+                          ppo_norm_adv=flags.ppo_norm_adv)
 
 
 def checkpoint_path(flags: Flags) -> str:
@@ -166,6 +169,7 @@ def resolve_runtime(flags: Flags, want_cuda: bool) -> str:
 
 
 def train(flags: Flags) -> dict:
+    _hparams(flags)  # refuses an unknown --algo / --ppo_epochs < 1 before anything starts
     want_cuda = flags.device == "cuda" or (flags.device == "auto" and torch.cuda.is_available())
     info = D.init_distributed(use_cuda=want_cuda, high_priority=flags.rccl_high_priority)
     dev = torch.device("cuda", info.local_rank) if want_cuda else torch.device("cpu")
@@ -216,7 +220,9 @@ def train(flags: Flags) -> dict:
         step, n_update = restore(ck, learner.model, learner.opt)
         learner.n_updates = n_update
         log(f"[microbeast_amd] resumed {ck_path} at step={step} update={n_update}")
-    logger = CsvLogger(flags.savedir, flags.exp_name, enabled=info.is_main, append=flags.resume)
+    ppo = flags.algo == "ppo"  # losses [7]: + approx_kl, clip_frac as trailing CSV columns
+    logger = CsvLogger(flags.savedir, flags.exp_name, enabled=info.is_main, append=flags.resume,
+                       extra_loss_columns=PPO_LOSS_COLUMNS if ppo else ())
 
     league = None
     if flags.self_play and runtime != "gpu":
@@ -292,7 +298,7 @@ def train(flags: Flags) -> dict:
         for lv, m in readout.pop(wait):
             logger.losses(m["update"], lv[0], lv[1], lv[2], lv[3], m["period"], m["step"],
                           m["fps"], m["wait_s"], m["learn_s"], lv[4], phase_ms=m["phase"],
-                          policy_lag=m["lag"])
+                          policy_lag=m["lag"], extra=lv[5:7] if ppo else ())
             last.update(update=m["update"], step=m["step"], pg_loss=lv[0], value_loss=lv[1],
                         entropy=lv[2], total_loss=lv[3], fps=m["fps"])
             log(f"update {m['update']} step {m['step']} total_loss {lv[3]:.4f} pg {lv[0]:.4f} "

@@ -11,7 +11,8 @@
   (fwd_ms, bwd_ms, allreduce_ms, optim_ms, publish_ms: HIP-event times read one
   update late, so logging them never synchronises the host with the GPU) and
   policy_lag (learner updates between the rollout's behaviour weights and the
-  update that consumed it).
+  update that consumed it). ``--algo ppo`` appends approx_kl and clip_frac after them
+  (``extra_loss_columns``); the IMPALA header and rows are unchanged.
 
 Only rank 0 writes (DP); rows are flushed per write so a killed run keeps
 its log.
@@ -26,6 +27,8 @@ PHASES = ("fwd", "bwd", "allreduce", "optim", "publish")
 LOSS_HEADER = ["update", "pg_loss", "value_loss", "entropy_loss", "total_loss", "update time",
                "frames", "fps", "wait_s", "learn_s", "mean_rho"] + [f"{p}_ms" for p in PHASES] + [
                "policy_lag"]
+# --algo ppo: two more trailing columns (the mean_rho column then holds the mean ratio)
+PPO_LOSS_COLUMNS = ["approx_kl", "clip_frac"]
 
 
 class PhaseTimer:
@@ -70,15 +73,21 @@ class PhaseTimer:
         for idx in (self._cur, self._cur ^ 1):
             evs = self._sets[idx]
             if len(evs) > 1 and evs[-1][1].query():
-                self._last = {n: evs[i - 1][1].elapsed_time(e) for i, (n, e) in enumerate(evs)
-                              if i > 0}
+                # marks of one name add up (a PPO update marks every phase once per epoch)
+                last: dict = {}
+                for i, (n, e) in enumerate(evs):
+                    if i > 0:
+                        last[n] = last.get(n, 0.0) + evs[i - 1][1].elapsed_time(e)
+                self._last = last
                 break
         return dict(self._last)
 
 
 class CsvLogger:
-    def __init__(self, savedir: str, exp_name: str, enabled: bool = True, append: bool = False):
+    def __init__(self, savedir: str, exp_name: str, enabled: bool = True, append: bool = False,
+                 extra_loss_columns=()):
         self.enabled = enabled
+        self.extra_loss_columns = list(extra_loss_columns)
         self.ep_path = os.path.join(savedir, f"{exp_name}.csv")
         self.loss_path = os.path.join(savedir, f"{exp_name}Losses.csv")
         self._ep = self._loss = None
@@ -95,7 +104,7 @@ class CsvLogger:
         if new_ep:
             self._epw.writerow(EPISODE_HEADER)
         if new_loss:
-            self._lossw.writerow(LOSS_HEADER)
+            self._lossw.writerow(LOSS_HEADER + self.extra_loss_columns)
         self._ep.flush()
         self._loss.flush()
         self.n_episodes = 0
@@ -112,14 +121,15 @@ class CsvLogger:
 
     def losses(self, update: int, pg: float, value: float, entropy: float, total: float,
                update_time: float, frames: int, fps: float, wait_s: float, learn_s: float,
-               mean_rho: float, phase_ms: dict | None = None, policy_lag: float = -1) -> None:
+               mean_rho: float, phase_ms: dict | None = None, policy_lag: float = -1,
+               extra=()) -> None:
         if not self.enabled:
             return
         ph = phase_ms or {}
         self._lossw.writerow([update, pg, value, entropy, total, update_time, frames,
                               round(fps, 2), round(wait_s, 6), round(learn_s, 6), mean_rho]
                              + [round(ph[p], 4) if p in ph else "" for p in PHASES]
-                             + [policy_lag])
+                             + [policy_lag] + list(extra))
         self._loss.flush()
 
     def close(self):

@@ -34,6 +34,9 @@ def main():
     ap.add_argument("--bwd_occ", type=int, default=0,
                     help="backward workgroups per CU (the GPU actor runtime's cap is 1; 0: none)")
     ap.add_argument("--fwd_occ", type=int, default=0, help="forward workgroups per CU (as --bwd_occ)")
+    ap.add_argument("--algo", default="impala", help="impala (V-trace) | ppo")
+    ap.add_argument("--ppo_epochs", type=int, default=1,
+                    help="--algo ppo: optimiser steps per update (the time printed is per update)")
     a = ap.parse_args()
     import torch
 
@@ -51,7 +54,8 @@ def main():
     flags = parse_flags(["--device", "cuda", "--arch", a.arch, "--env_size", str(a.size),
                          "--quiet"], interactive=False)
     torch.manual_seed(0)
-    learner = Learner(make_model(flags, dev), LearnerHParams(), dev)
+    learner = Learner(make_model(flags, dev),
+                      LearnerHParams(algo=a.algo, ppo_epochs=a.ppo_epochs), dev)
     S, T, B = a.size * a.size, a.T, a.batch
     g = torch.Generator(device=dev).manual_seed(1)
     # sparse legal-action masks with --active of the cells live, like the engine's rollouts
