@@ -88,6 +88,9 @@ _SIGS = {
     "mbk_conv_wgrad": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                        c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "mbk_conv_wgrad_parts": [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int],
+    "mbk_conv_wgrad0_sparse_parts": [c_int],
+    "mbk_conv_wgrad0_sparse": [c_void_p, c_void_p, c_void_p, ctypes.c_uint, c_void_p, c_int, c_int,
+                               c_void_p],
     "mbk_pool_conv_bwd_parts": [c_int, c_int, c_int, c_int, c_int],
     "mbk_pool_conv_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                           c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],

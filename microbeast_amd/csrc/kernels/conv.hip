@@ -1196,6 +1196,247 @@ __global__ __launch_bounds__(kThreads) void conv_wgrad_kernel(ConvWgradArgs a) {
   }
 }
 
+// ------------------------------------------------------------------ stage-0 weight gradient, sparse
+// The UNPOOL case above (bit planes, 32 -> 16 channels, 16x16 map) summed over the non-empty
+// cells only. With e the empty cell's word, X = E + D: E = e in every in-map cell, D = X - E is
+// zero except at the cells whose word differs from e (entries -1 / 0 / +1), and for tap t
+//   dW[t][ci][co] = E[ci] S_t[co] + sum_{q: x_q != e} D[q][ci] dY[q - off_t][co]
+//   S_t[co] = sum_{p, p + off_t in map} dY[p][co]                  (S_4 = the bias gradient)
+// for any observation and any e (a dense image lists all 256 cells). Per image: 8 MFMAs for
+// S_t (A = the unshifted dY K block, B = an in-map indicator whose column t is tap t) and 18 per
+// block of 32 listed cells (A = dY gathered at the cells' tap-shifted pixels, one free row
+// address per lane of the transposed read; B = the D rows, built in registers from the block's
+// words), against 152 and a staged 16 KB X tile.
+// Waves own whole images (no workgroup barrier in the loop): a wave's LDS is its halo'd dY tile
+// in the TSH layout above (halo and row pad zeroed once; the scatter is the UNPOOL round's, so
+// every element holds the same bf16) and one block's list (32 words x ^ e, 32 tile offsets).
+// The next image's words, dp and argmax bytes load into registers while this one computes.
+struct Wgrad0SparseArgs {
+  const uint32_t* x;    // [N][256] observation words
+  const bf16* dp;       // [N][8][8][16]
+  const uint8_t* pidx;  // [N][8][8][16]
+  float* partial;       // [gridDim.x][16 * 288 + 16], conv_wgrad_kernel's row layout
+  int N;
+  uint32_t empty;
+  int* queue;  // per-wave image queue (common.h; the kQueueWgrad site), null: static stride
+};
+// 3 waves: 2 workgroups' LDS (2 x 34.3 KB) fit beside an 80 KB acting workgroup
+constexpr int kS0Waves = 3, kS0Threads = 64 * kS0Waves;
+constexpr int kS0Rbd = wg_rbd<32, 16>();                  // 640: 18 halo'd pixels + 2 of row pad
+constexpr int kS0Tile = 18 * kS0Rbd;                      // halo'd dY tile
+constexpr int kS0WaveLds = kS0Tile + 32 * 4 + 32 * 2;     // + the block's words and offsets
+constexpr int kS0Smem = kS0Waves * kS0WaveLds;            // (>= the final reduce's 18.6 KB)
+static_assert(kS0WaveLds % 16 == 0 && kS0Smem >= (16 * 288 + kS0Waves * 16) * 4, "LDS carve");
+static_assert(2 * kS0Smem + 80 * 1024 <= 160 * 1024, "two workgroups beside an acting one");
+
+struct S0Img {  // one image's operands, per lane: cells 64 j + lane; (window k, 4 channels) x 4 phases
+  uint32_t w0, w1, w2, w3;
+  uint2 d0, d1, d2, d3;
+  uint32_t i0, i1, i2, i3;
+};
+__device__ __forceinline__ S0Img s0_load(const Wgrad0SparseArgs& a, int img, int lane) {
+  S0Img f;
+  const uint32_t* xw = a.x + (size_t)img * 256 + lane;
+  f.w0 = xw[0]; f.w1 = xw[64]; f.w2 = xw[128]; f.w3 = xw[192];
+  // phase ph: window (oy, ox) = (2 (k / 4) + ph / 2, 2 (k % 4) + ph % 2), k = lane / 4
+  const int k = lane >> 2;
+  const size_t o = ((size_t)img * 64 + 16 * (k >> 2) + 2 * (k & 3)) * 16 + 4 * (lane & 3);
+  f.d0 = *(const uint2*)(a.dp + o);       f.i0 = *(const uint32_t*)(a.pidx + o);
+  f.d1 = *(const uint2*)(a.dp + o + 16);  f.i1 = *(const uint32_t*)(a.pidx + o + 16);
+  f.d2 = *(const uint2*)(a.dp + o + 128); f.i2 = *(const uint32_t*)(a.pidx + o + 128);
+  f.d3 = *(const uint2*)(a.dp + o + 144); f.i3 = *(const uint32_t*)(a.pidx + o + 144);
+  return f;
+}
+// one window-parity phase of the pool backward: the lane's 4 channels of window (oy, ox), in
+// conv_wgrad_kernel's form (fp32 add, bf16 store); dimg = interior pixel (0, 0). The argmax
+// byte is clamped to the 3x3 window, so no byte addresses LDS outside the tile.
+__device__ __forceinline__ void s0_scatter(char* dimg, int oy, int ox, int c0, uint2 d, uint32_t ix) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int t = min((int)((ix >> (8 * j)) & 0xFFu), 8);
+    const int ky = (t * 11) >> 5, kx = t - 3 * ky;  // t / 3 for t < 9
+    const int py = 2 * oy - 1 + ky, px = 2 * ox - 1 + kx;
+    uint16_t* el = (uint16_t*)(dimg + py * kS0Rbd + px * 32 + (c0 + j) * 2);
+    const uint32_t d2 = j < 2 ? d.x : d.y;
+    const float add = __uint_as_float((j & 1) ? (d2 & 0xFFFF0000u) : (d2 << 16));
+    const float v = __uint_as_float((uint32_t)*el << 16) + add;
+    *el = __bfloat16_as_ushort(f2bf(v));
+  }
+  asm volatile("" ::: "memory");
+}
+// two list entries' D values of one plane (bit): 0, or k1 = +-1.0 as bf16 (the sign by e's bit)
+__device__ __forceinline__ uint32_t s0_pair(uint32_t x0, uint32_t x1, uint32_t bit, uint32_t k1) {
+  return ((x0 & bit) ? k1 : 0u) | ((x1 & bit) ? k1 << 16 : 0u);
+}
+
+__global__ __launch_bounds__(kS0Threads) void wgrad0_sparse_kernel(Wgrad0SparseArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int RBD = kS0Rbd, DPB = 32, DIN = RBD + DPB, KTOT = 9 * 32, COUT = 16;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int G = lane >> 4, li = lane & 15;
+  char* const tile = smem + wave * kS0WaveLds;
+  uint32_t* const lw = (uint32_t*)(tile + kS0Tile);        // the block's 32 words x ^ e
+  uint16_t* const lp = (uint16_t*)(tile + kS0Tile + 128);  // their pixels' tile byte offsets
+  for (int e = lane; e < kS0WaveLds / 16; e += 64) ((uint4*)tile)[e] = make_uint4(0, 0, 0, 0);
+
+  f32x4 acc[18], accs = f32x4{0.f, 0.f, 0.f, 0.f};  // acc[t * 2 + cb] as conv_wgrad_kernel; S_t
+#pragma unroll
+  for (int nb = 0; nb < 18; ++nb) acc[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // D fragment constants of this lane's planes li and li + 16: e's bit there makes the entry -1
+  const uint32_t bit0 = 1u << li, bit1 = 1u << (li + 16);
+  const uint32_t k0 = (a.empty & bit0) ? 0xBF80u : 0x3F80u, k1 = (a.empty & bit1) ? 0xBF80u : 0x3F80u;
+  // S_t indicator fragments (B: K = the block's 4 rows x 8 columns, lane group G = row G, the
+  // lane's 8 values = the 8 columns; N = tap li < 9): 1 where pixel + off_t is in the map.
+  // Only map column 0 (tap column 0), map column 15 (tap column 2) and the first / last map
+  // row (tap rows 0 / 2) drop out.
+  const int tky = li / 3, tkx = li - 3 * tky;
+  const uint32_t one2 = li < 9 ? 0x3F803F80u : 0u;
+  uint4 ind0 = make_uint4(one2, one2, one2, one2), ind1 = ind0;  // column chunks 0-7, 8-15
+  if (tkx == 0) ind0.x &= 0xFFFF0000u;
+  if (tkx == 2) ind1.w &= 0x0000FFFFu;
+  const bool rowz0 = G == 0 && tky == 0, rowz3 = G == 3 && tky == 2;
+  const int sk = lane >> 2, sc0 = 4 * (lane & 3), soy = 2 * (sk >> 2), sox = 2 * (sk & 3);
+
+  // one full (or zero-padded) block of 32 listed cells: 18 MFMAs
+  auto flush = [&]() {
+    asm volatile("" ::: "memory");
+    const uint4 wa = *(const uint4*)(lw + 8 * G), wb = *(const uint4*)(lw + 8 * G + 4);
+    const char* a0 = tile + lp[8 * G + (li >> 2)] + 8 * (li & 3);
+    const char* a1 = tile + lp[8 * G + 4 + (li >> 2)] + 8 * (li & 3);
+    Frag8 b0, b1;
+    b0.u = make_uint4(s0_pair(wa.x, wa.y, bit0, k0), s0_pair(wa.z, wa.w, bit0, k0),
+                      s0_pair(wb.x, wb.y, bit0, k0), s0_pair(wb.z, wb.w, bit0, k0));
+    b1.u = make_uint4(s0_pair(wa.x, wa.y, bit1, k1), s0_pair(wa.z, wa.w, bit1, k1),
+                      s0_pair(wb.x, wb.y, bit1, k1), s0_pair(wb.z, wb.w, bit1, k1));
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      // tap t's dY at q - off_t = halo'd (y + 2 - t / 3, x + 2 - t % 3), as the TSH form
+      const int off = (2 - t / 3) * RBD + (2 - t % 3) * DPB;
+      Frag8 at;
+      at.h[0] = tr_read(a0 + off);
+      at.h[1] = tr_read(a1 + off);
+      acc[2 * t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at.v, b0.v, acc[2 * t], 0, 0, 0);
+      acc[2 * t + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at.v, b1.v, acc[2 * t + 1], 0, 0, 0);
+    }
+    asm volatile("" ::: "memory");
+  };
+  int fill = 0;  // entries in the open block (wave-uniform)
+  // cells 64 j + lane: append the non-empty ones in cell order, running every block that fills
+  auto pass = [&](uint32_t w, int j) {
+    const uint32_t nz = w ^ a.empty;
+    const uint64_t m = __ballot(nz != 0u);
+    if (m == 0) return;
+    const int pre = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    int slot = nz != 0u ? fill + pre : -1;
+    int total = fill + __popcll(m);
+    const int cell = 64 * j + lane;
+    const uint16_t off = (uint16_t)((cell >> 4) * RBD + (cell & 15) * DPB);
+    for (;;) {
+      if (slot >= 0 && slot < 32) {
+        lw[slot] = nz;
+        lp[slot] = off;
+      }
+      if (total < 32) break;
+      flush();
+      slot -= 32;
+      total -= 32;
+    }
+    fill = total;
+  };
+
+  const int nwaves = (int)gridDim.x * kS0Waves;
+  int cend = 0;
+  int img = a.queue ? mbk::wave_next_item(a.queue, -1, cend, a.N) : (int)blockIdx.x * kS0Waves + wave;
+  img = __builtin_amdgcn_readfirstlane(img);
+  S0Img nx{};
+  if (img < a.N) nx = s0_load(a, img, lane);
+  while (img < a.N) {
+    const S0Img cu = nx;
+    int nimg = a.queue ? mbk::wave_next_item(a.queue, img, cend, a.N) : img + nwaves;
+    nimg = __builtin_amdgcn_readfirstlane(nimg);
+    if (nimg < a.N) nx = s0_load(a, nimg, lane);
+    // dY tile: zero the interior (16 rows x 512 bytes), then the four parity phases
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int e = lane + 64 * i;
+      *(uint4*)(tile + DIN + (e >> 5) * RBD + (e & 31) * 16) = make_uint4(0, 0, 0, 0);
+    }
+    asm volatile("" ::: "memory");
+    s0_scatter(tile + DIN, soy, sox, sc0, cu.d0, cu.i0);
+    s0_scatter(tile + DIN, soy, sox + 1, sc0, cu.d1, cu.i1);
+    s0_scatter(tile + DIN, soy + 1, sox, sc0, cu.d2, cu.i2);
+    s0_scatter(tile + DIN, soy + 1, sox + 1, sc0, cu.d3, cu.i3);
+    // S_t (column 4: every pixel, the bias gradient)
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const char* db = tile + DIN + (4 * b + G) * RBD + (8 * c + (li >> 2)) * DPB + 8 * (li & 3);
+        Frag8 at, in;
+        at.h[0] = tr_read(db);
+        at.h[1] = tr_read(db + 4 * DPB);
+        in.u = c ? ind1 : ind0;
+        if ((b == 0 && rowz0) || (b == 3 && rowz3)) in.u = make_uint4(0, 0, 0, 0);
+        accs = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at.v, in.v, accs, 0, 0, 0);
+      }
+    pass(cu.w0, 0);
+    pass(cu.w1, 1);
+    pass(cu.w2, 2);
+    pass(cu.w3, 3);
+    if (fill > 0) {
+      // pad the last block: zero D rows, and a pixel whose 9 taps read the tile's never-written
+      // halo column 17 and row pad (rows 0-2), so the padding adds exactly nothing
+      if (lane >= fill && lane < 32) {
+        lw[lane] = 0u;
+        lp[lane] = (uint16_t)(17 * DPB);
+      }
+      flush();
+      fill = 0;
+    }
+    img = nimg;
+  }
+  if (a.queue) mbk::wave_queue_done(a.queue, nwaves);
+
+  // the E term: acc[t][ci][co] += E[ci] S_t[co]; S_t[co = 4G + i] is accs[i] of lane (G, t)
+  const float e0 = (a.empty & bit0) ? 1.f : 0.f, e1 = (a.empty & bit1) ? 1.f : 0.f;
+#pragma unroll
+  for (int t = 0; t < 9; ++t)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float s = __shfl(accs[i], 16 * G + t, 64);
+      acc[2 * t][i] += e0 * s;
+      acc[2 * t + 1][i] += e1 * s;
+    }
+  // ---- reduce the waves through LDS in wave order, as conv_wgrad_kernel
+  __syncthreads();  // every wave is done with its tile
+  float* red = (float*)smem;  // [COUT][KTOT], then [waves][COUT] bias sums
+  for (int w = 0; w < kS0Waves; ++w) {
+    if (wave == w) {
+#pragma unroll
+      for (int nb = 0; nb < 18; ++nb)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          float* p = red + (4 * G + i) * KTOT + nb * 16 + li;  // C layout: row co, column n
+          *p = (w == 0 ? 0.f : *p) + acc[nb][i];
+        }
+    }
+    __syncthreads();
+  }
+  float* bred = red + COUT * KTOT;
+  if (li == 4) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) bred[wave * COUT + 4 * G + i] = accs[i];
+  }
+  __syncthreads();
+  float* out = a.partial + (size_t)blockIdx.x * (COUT * KTOT + COUT);
+  for (int e = tid; e < COUT * KTOT / 4; e += kS0Threads) ((float4*)out)[e] = ((const float4*)red)[e];
+  if (tid < COUT) {
+    float s = 0.f;
+    for (int w = 0; w < kS0Waves; ++w) s += bred[w * COUT + tid];
+    out[COUT * KTOT + tid] = s;
+  }
+}
+
 // partial[nparts][COUT*9*CIN + COUT] -> dw[co][ci][ky][kx] (+)=, db[co] (+)=
 // block = 64 output columns x 4 part-lanes over parts [y*pps, (y+1)*pps); with `stage`
 // set the split sums go to stage[y][row] for a second pass (two-level: the persistent
@@ -1515,7 +1756,7 @@ int g_conv0_row = 1;   // stage-0 conv of 16-wide maps on conv0_row_kernel (0: g
 
 // resident workgroups the whole device holds for (kernel, dynamic LDS)
 // (occ: mbk_occ_f / mbk_occ_b, the forward / backward per-CU caps of common.h)
-int resident_blocks(const void* kfn, size_t sm, int (*occ)(int) = nullptr) {
+int resident_blocks(const void* kfn, size_t sm, int (*occ)(int) = nullptr, int threads = kThreads) {
   static int cus = 0;
   if (!cus) {
     int dev = 0;
@@ -1525,7 +1766,7 @@ int resident_blocks(const void* kfn, size_t sm, int (*occ)(int) = nullptr) {
   }
   if (sm > 64 * 1024) hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
   int per = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kfn, kThreads, sm) != hipSuccess || per < 1)
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kfn, threads, sm) != hipSuccess || per < 1)
     per = 1;
   int r = cus * (occ ? occ(per) : per);
   if (g_grid_cap > 0 && r > g_grid_cap) r = g_grid_cap;
@@ -1712,6 +1953,28 @@ extern "C" int mbk_conv_wgrad(const void* x, int in_bits, int cin, int cout, con
   else if (cin == 32 && cout == 32) LAUNCH(32, 32, false);
   else return (int)hipErrorInvalidValue;
 #undef LAUNCH
+  return (int)hipGetLastError();
+}
+
+// The sparse stage-0 form (wgrad0_sparse_kernel: 16x16 bit-plane maps, 32 -> 16 channels, dY =
+// the pool backward of dp through pidx): partial rows it writes for N images, one per workgroup.
+// Two workgroups per unit of the backward cap, as the dense pool-fused form above.
+extern "C" int mbk_conv_wgrad0_sparse_parts(int N) {
+  if (N < 1) return -(int)hipErrorInvalidValue;
+  const int res = resident_blocks((const void*)wgrad0_sparse_kernel, kS0Smem, occ_b2, kS0Threads);
+  return (int)std::max(1L, std::min((long)(N + kS0Waves - 1) / kS0Waves, (long)res));
+}
+
+// empty_word: the observation word of an empty cell (any value is correct: cells that differ
+// from it are the ones summed one by one). Rows of `partial` as mbk_conv_wgrad's.
+extern "C" int mbk_conv_wgrad0_sparse(const void* x, const void* dp, const void* pidx,
+                                      unsigned empty_word, float* partial, int nparts, int N,
+                                      hipStream_t stream) {
+  if (!x || !dp || !pidx || !partial || nparts < 1 || N < 1) return (int)hipErrorInvalidValue;
+  Wgrad0SparseArgs a{(const uint32_t*)x, (const bf16*)dp, (const uint8_t*)pidx, partial, N,
+                     empty_word, nullptr};
+  if (MBK_WGRAD_QUEUE) a.queue = mbk_work_queue(stream, kQueueWgrad);
+  hipLaunchKernelGGL(wgrad0_sparse_kernel, dim3(nparts), dim3(kS0Threads), kS0Smem, stream, a);
   return (int)hipGetLastError();
 }
 

@@ -56,6 +56,12 @@ def _nch(c: int) -> int:
     return 5 if c == 16 else 9
 
 
+# the observation's one-hot plane groups (first plane, planes): hp, resources, owner, unit type,
+# action. An empty cell is the first plane of every group (hp 0, resources 0, no owner, no
+# type, noop): the word the sparse stage-0 weight gradient does not list (conv.hip)
+PLANE_GROUPS = ((0, 5), (5, 5), (10, 3), (13, 8), (21, 6))
+EMPTY_WORD = sum(1 << off for off, _ in PLANE_GROUPS)
+
 _PF_FWD = 8 * 256    # conv_fwd register-prefetch capacity (elements per group)
 _PF_WGRAD = 4 * 256  # conv_wgrad prefetch capacity, X and dY each
 # conv_fwd workgroup sizing (tools/microbench.py sweeps): LDS budget per workgroup (48 KB =
@@ -162,6 +168,10 @@ class HipEncoder:
         # LDS staging (16-wide maps; bit-identical): no pool_bwd_idx launch, no 4.3 GB
         # full-resolution gradient in HBM per 524K-frame update
         self.fused_pool_wgrad0 = True
+        # that weight gradient summed over the non-empty cells only (conv.hip
+        # wgrad0_sparse_kernel: 26 MFMAs per image with <= 32 such cells against 152, no X tile;
+        # equal up to fp32 summation order). False: the dense pool-fused kernel
+        self.sparse_wgrad0 = True
         # images per round of the pool-fused stage-0 weight gradient: 1 (36 KB of LDS, so two
         # of its workgroups fit beside an acting one under the backward cap: learner 17.63 ->
         # 16.94 ms at cap 1, bwd inside the bench 16.3 -> 15.4 ms over 3 seed pairs, profile
@@ -326,6 +336,22 @@ class HipEncoder:
         N.check(k.mbk_conv_wgrad(x.data_ptr(), int(L.bits), L.cin, L.cout, N.ptr(dy),
                                  N.ptr(dp), N.ptr(pidx), part.data_ptr(), nparts, n,
                                  L.H, L.W, imgs, int(L.relu_in), st), "conv_wgrad")
+        self._reduce(part.data_ptr(), nparts, L, dw, db)
+
+    def _wgrad0_sparse(self, L: ConvLayer, x, dp, pidx, dw: torch.Tensor, db: torch.Tensor):
+        """The stage-0 layer's weight gradient from the non-empty cells (16x16 bit-plane maps):
+        the partial rows have ``_wgrad``'s layout and go through the same reduce."""
+        n = x.shape[0]
+        k = N.kernels()
+        nparts = k.mbk_conv_wgrad0_sparse_parts(n)
+        if nparts < 1:
+            raise RuntimeError(f"conv_wgrad0_sparse: unsupported batch {n}")
+        row = L.cout * 9 * L.cin + L.cout
+        need = (nparts + (nparts + 31) // 32) * row  # + the two-level reduce's scratch rows
+        part = self._partials(L, need, x.device)
+        N.check(k.mbk_conv_wgrad0_sparse(x.data_ptr(), dp.data_ptr(), pidx.data_ptr(), EMPTY_WORD,
+                                         part.data_ptr(), nparts, n, N.stream_ptr()),
+                "conv_wgrad0_sparse")
         self._reduce(part.data_ptr(), nparts, L, dw, db)
 
     def _partials(self, L: ConvLayer, need: int, device) -> torch.Tensor:
@@ -607,7 +633,10 @@ class HipEncoder:
                     and N.kernels().mbk_conv_wgrad_parts(
                         int(Ls.bits), Ls.cin, Ls.cout, x.shape[0], Ls.H, Ls.W,
                         _imgs_wgrad(Ls, True, self.wgrad0_imgs), 1) > 0):
-                self._wgrad(Ls, x, None, grads[2 * li], grads[2 * li + 1], dp=dp, pidx=pidx)
+                if self.sparse_wgrad0 and (Ls.H, Ls.cin, Ls.cout) == (16, 32, 16):
+                    self._wgrad0_sparse(Ls, x, dp, pidx, grads[2 * li], grads[2 * li + 1])
+                else:
+                    self._wgrad(Ls, x, None, grads[2 * li], grads[2 * li + 1], dp=dp, pidx=pidx)
                 g = None
                 continue
             if (s > 0 and self.fused_pool_conv_bwd and x.is_cuda

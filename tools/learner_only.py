@@ -24,6 +24,10 @@ def main():
     ap.add_argument("--active", type=float, default=0.007,
                     help="fraction of (frame, cell) pairs with a legal action: 0.007 ~ the random-"
                          "init policy's early game, 0.025 ~ a settled training run (6.5 / 256)")
+    ap.add_argument("--occupied", type=float, default=None, metavar="MEAN",
+                    help="observations like a rollout's: every cell the empty word except about "
+                         "MEAN cells per frame with random one-hot words (a settled run has 19.5 "
+                         "of 256); default: uniformly random words, every cell non-empty")
     ap.add_argument("--no_abits", action="store_true",
                     help="no active-cell bitmap rows in the batch (the head counts from masks)")
     ap.add_argument("--set", action="append", default=[],
@@ -63,8 +67,18 @@ def main():
     act = torch.rand(T + 1, B, S, device=dev, generator=g) < a.active
     mask[..., 0] = torch.where(act, torch.randint(1, 2 ** 31 - 1, (T + 1, B, S), device=dev,
                                                   generator=g, dtype=torch.int32), 0)
+    obs = torch.randint(0, 2 ** 26, (T + 1, B, S), dtype=torch.int32, device=dev, generator=g)
+    if a.occupied is not None:
+        from microbeast_amd.ops.encoder import EMPTY_WORD, PLANE_GROUPS
+        word = torch.zeros(T + 1, B, S, dtype=torch.int32, device=dev)
+        for off, k in PLANE_GROUPS:
+            word |= 1 << (off + torch.randint(0, k, (T + 1, B, S), dtype=torch.int32, device=dev,
+                                              generator=g))
+        occ = torch.rand(T + 1, B, S, device=dev, generator=g) < a.occupied / S
+        obs = torch.where(occ, word, EMPTY_WORD)
+        del word, occ
     batch = {
-        "obs": torch.randint(0, 2 ** 26, (T + 1, B, S), dtype=torch.int32, device=dev, generator=g),
+        "obs": obs,
         "mask": mask,
         "action": torch.zeros(T + 1, B, S, 7, dtype=torch.uint8, device=dev),
         "logp": -torch.rand(T + 1, B, device=dev, generator=g),
