@@ -93,8 +93,7 @@ _SIGS = {
                                c_void_p],
     "mbk_pool_conv_bwd_parts": [c_int, c_int, c_int, c_int, c_int],
     "mbk_pool_conv_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                          c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    "mbk_pool_conv_bwd_partial_floats": [c_int, c_int, c_int],
+                          c_int, c_int, c_int, c_int, c_int, c_void_p],
     "mbk_conv_set_grid_cap": [c_int],
     "mbk_set_learner_occupancy": [c_int, c_int],
     "mbk_set_work_queues": [c_int],
@@ -107,8 +106,7 @@ _SIGS = {
                    c_void_p, c_void_p, c_void_p],
     "mbk_gemm_nt": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                     c_int, c_int, c_int, c_int, c_void_p],
-    "mbk_wgrad_reduce": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
-                         c_void_p],
+    "mbk_wgrad_partial_floats": [c_int, c_int, c_int],
     "mbk_wgrad_reduce_batch": [c_void_p, c_int, c_void_p],
     "mbk_pool_bwd": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "mbk_conv_pack": [c_void_p, c_int, c_void_p],
@@ -153,10 +151,8 @@ _SIGS = {
     "mbk_pack_env_actions": [c_void_p, c_int64, c_void_p, c_void_p],
     "mbk_res_bwd16_parts": [c_int, c_int, c_int, c_int],
     "mbk_res_bwd32_parts": [c_int, c_int, c_int, c_int],
-    "mbk_res_bwd32_partial_floats": [c_int],
     "mbk_res_bwd32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                      c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                      c_int, c_void_p],
+                      c_int, c_int, c_int, c_int, c_void_p],
     "mbk_res_fwd16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                       c_int, c_int, c_int, c_void_p],
     "mbk_res_fwd16_stage": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -170,10 +166,8 @@ _SIGS = {
     "mbk_res_bwd32_team_parts": [c_int, c_int, c_int],
     "mbk_res_bwd32_team": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                            c_int, c_int, c_int, c_int, c_void_p],
-    "mbk_res_bwd16_partial_floats": [c_int],
     "mbk_res_bwd16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                      c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                      c_int, c_void_p],
+                      c_int, c_int, c_int, c_int, c_void_p],
     # gridnet.hip
     "mbk_bits_pad": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "mbk_colsum_parts": [c_int64],
@@ -195,8 +189,7 @@ _SIGS = {
     "mbk_gemm_nt_mask": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                          c_int, c_int, c_int, c_void_p, c_void_p],
 }
-_RESTYPE = {"mbk_res_bwd16_partial_floats": c_int64, "mbk_res_bwd32_partial_floats": c_int64,
-            "mbk_pool_conv_bwd_partial_floats": c_int64}
+_RESTYPE = {"mbk_wgrad_partial_floats": c_int64}
 
 
 def _ensure_built() -> None:

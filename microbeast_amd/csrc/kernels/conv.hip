@@ -28,6 +28,7 @@
 // chunk = tap (Cin 32) or tap pair (Cin 16: k = h*16 + ci for tap 2c+h).
 #include "../include/mbk_api.h"
 #include "common.h"
+#include "launch.h"
 
 #include <algorithm>
 #include <map>
@@ -1437,7 +1438,7 @@ __global__ __launch_bounds__(kS0Threads) void wgrad0_sparse_kernel(Wgrad0SparseA
   }
 }
 
-// partial[nparts][COUT*9*CIN + COUT] -> dw[co][ci][ky][kx] (+)=, db[co] (+)=
+// partial[nparts][COUT*9*CIN + COUT] -> dw[co][ci][ky][kx], db[co] (overwritten)
 // block = 64 output columns x 4 part-lanes over parts [y*pps, (y+1)*pps); with `stage`
 // set the split sums go to stage[y][row] for a second pass (two-level: the persistent
 // wgrad writes up to a few thousand partial rows). Fixed summation order (deterministic).
@@ -1448,8 +1449,7 @@ __device__ __forceinline__ void wgrad_reduce_cols(const float* __restrict__ part
                                                   int pps, int split, int colblk,
                                                   float* __restrict__ stage, int cin,
                                                   int cin_real, int cout, float* __restrict__ dw,
-                                                  float* __restrict__ db, int accumulate,
-                                                  float (*red)[64]) {
+                                                  float* __restrict__ db, float (*red)[64]) {
   const int ktot = 9 * cin, row = cout * ktot + cout;
   const int col = threadIdx.x & 63, pl = threadIdx.x >> 6;
   const int e = colblk * 64 + col;
@@ -1471,35 +1471,24 @@ __device__ __forceinline__ void wgrad_reduce_cols(const float* __restrict__ part
     const int co = e / ktot, r = e - co * ktot, t = r / cin, ci = r - t * cin;
     if (ci >= cin_real) return;
     float* d = dw + ((size_t)co * cin_real + ci) * 9 + t;
-    *d = accumulate ? *d + s : s;
+    *d = s;
   } else if (db) {
     const int co = e - cout * ktot;
-    db[co] = accumulate ? db[co] + s : s;
+    db[co] = s;
   }
-}
-
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ partial,
-                                                           int nparts, int pps,
-                                                           float* __restrict__ stage, int cin,
-                                                           int cin_real, int cout,
-                                                           float* __restrict__ dw,
-                                                           float* __restrict__ db, int accumulate) {
-  __shared__ float red[4][64];
-  wgrad_reduce_cols(partial, nparts, pps, blockIdx.y, blockIdx.x, stage, cin, cin_real, cout, dw,
-                    db, accumulate, red);
 }
 
 // Many layers' reductions in one launch (blockIdx.z = job; the encoder defers every weight
 // gradient reduce of a backward pass to one mbk_wgrad_reduce_batch call). Level 0 runs a
 // job's split sums (two-level jobs) or its whole sum; level 1 the two-level jobs' second
-// stage: per element the same adds in the same order as mbk_wgrad_reduce -> bit-identical.
+// stage: per element the same adds in the same order however the jobs are batched ->
+// bit-identical. The buffer contract (rows, then scratch rows) is launch.h's.
 struct MbkReduceJob {
   const float* partial;
   float* dw;
   float* db;
-  int nparts, cin, cin_real, cout, accumulate;
+  int nparts, cin, cin_real, cout;
 };
-constexpr int kReducePps = 32;
 constexpr int kMaxReduceJobs = 32;
 struct ReduceBatch {
   MbkReduceJob j[kMaxReduceJobs];
@@ -1508,19 +1497,19 @@ struct ReduceBatch {
 __global__ __launch_bounds__(256) void wgrad_reduce_batch_kernel(ReduceBatch b, int level) {
   __shared__ float red[4][64];
   const MbkReduceJob J = b.j[blockIdx.z];
-  const int row = J.cout * 9 * J.cin + J.cout;
+  const int row = mbk::wgrad_row_floats(J.cin, J.cout);
   if ((int)blockIdx.x * 64 >= row) return;  // whole workgroup: before any barrier
   const bool two = J.nparts > 2 * kReducePps;
-  const int splits = two ? (J.nparts + kReducePps - 1) / kReducePps : 1;
+  const int splits = two ? mbk::wgrad_reduce_splits(J.nparts) : 1;
   float* stage = two ? (float*)J.partial + (size_t)J.nparts * row : nullptr;
   if (level == 0) {
     if ((int)blockIdx.y >= splits) return;
     wgrad_reduce_cols(J.partial, J.nparts, two ? kReducePps : J.nparts, blockIdx.y, blockIdx.x,
-                      stage, J.cin, J.cin_real, J.cout, J.dw, J.db, J.accumulate, red);
+                      stage, J.cin, J.cin_real, J.cout, J.dw, J.db, red);
   } else {
     if (!two || blockIdx.y != 0) return;
     wgrad_reduce_cols(stage, splits, splits, 0, blockIdx.x, nullptr, J.cin, J.cin_real, J.cout,
-                      J.dw, J.db, J.accumulate, red);
+                      J.dw, J.db, red);
   }
 }
 
@@ -1733,17 +1722,16 @@ __global__ __launch_bounds__(256) void conv_pack_fp8_kernel(PackJobs8 jobs) {
   if (threadIdx.x == 0) J.scale[co] = ldexpf(1.f, -k);
 }
 
-inline size_t fwd_smem(int cin, bool bits, int imgs, int H, int W, int cout, bool pool,
-                       bool fp8 = false) {
-  (void)bits;  // bit planes are staged expanded (cin = 32)
+// (bit planes are staged expanded: cin = 32)
+inline size_t fwd_smem(int cin, int imgs, int H, int W, int cout, bool pool, bool fp8 = false) {
   const int pixb = fp8 ? cin + 8 : cin * 2 + 16;
   size_t t = (((size_t)imgs * (H + 2) * (W + 2) * pixb) + 15) & ~(size_t)15;
   if (pool) t += (size_t)imgs * H * W * (cout + 4) * 2;
   return t;
 }
 
-inline size_t wgrad_smem(int cin, int cout, int imgs, int H, int W, bool unpool = false) {
-  (void)unpool;  // (the pool-fused form keeps its pooled operands in registers)
+// (the same for the pool-fused form: it keeps its pooled operands in registers)
+inline size_t wgrad_smem(int cin, int cout, int imgs, int H, int W) {
   size_t t = wg_tile_bytes(cin, cout, imgs, H, W, wg_band_w(H, W));
   t += 4096;  // bit-plane lookup table (allocated for every variant: keeps the sizing simple)
   t += 64;    // the work queue's round ring
@@ -1754,30 +1742,18 @@ inline size_t wgrad_smem(int cin, int cout, int imgs, int H, int W, bool unpool 
 int g_grid_cap = 0;    // tests force multi-group workgroups with a small cap
 int g_conv0_row = 1;   // stage-0 conv of 16-wide maps on conv0_row_kernel (0: generic kernel)
 
-// resident workgroups the whole device holds for (kernel, dynamic LDS)
-// (occ: mbk_occ_f / mbk_occ_b, the forward / backward per-CU caps of common.h)
-int resident_blocks(const void* kfn, size_t sm, int (*occ)(int) = nullptr, int threads = kThreads) {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipGetDevice(&dev);
-    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
-  }
-  if (sm > 64 * 1024) hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-  int per = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kfn, threads, sm) != hipSuccess || per < 1)
-    per = 1;
-  int r = cus * (occ ? occ(per) : per);
-  if (g_grid_cap > 0 && r > g_grid_cap) r = g_grid_cap;
-  return r;
+// resident workgroups the whole device holds for (kernel, dynamic LDS), launch.h, under the
+// tests' grid cap (this file's conv kernels only)
+int capped_resident_blocks(const void* kfn, int threads, size_t sm, int (*occ)(int)) {
+  const int r = resident_blocks(kfn, threads, sm, occ);
+  return g_grid_cap > 0 && r > g_grid_cap ? g_grid_cap : r;
 }
 
 // Forward / dgrad grids: persistent, one resident set of workgroups that walks the image
 // groups (2x / 4x grids that retire workgroups early for the acting step measured level or
 // slower on the bench: DESIGN.md §9 rejected variants)
 int fwd_grid(int ngroups, const void* kfn, size_t sm) {
-  const long r = (long)resident_blocks(kfn, sm, mbk_occ_f);
+  const long r = (long)capped_resident_blocks(kfn, kThreads, sm, mbk_occ_f);
   return (int)std::max(1L, std::min((long)ngroups, r));
 }
 
@@ -1802,15 +1778,13 @@ static int conv_fwd_launch(const void* x, int in_bits, int cin, int cout, const 
   if (!index_math_ok(imgs, H, W)) return (int)hipErrorInvalidValue;
   ConvFwdArgs a{x, (const bf16*)w, bias, (const bf16*)add, (const bf16*)mask_src, (bf16*)y,
                 (bf16*)y_full, (uint8_t*)pool_idx, N, H, W, imgs, relu_in, pool, wscale};
-  const size_t sm = fwd_smem(cin, in_bits != 0, imgs, H, W, cout, pool != 0, fp8);
+  const size_t sm = fwd_smem(cin, imgs, H, W, cout, pool != 0, fp8);
   if (sm > 160 * 1024) return (int)hipErrorInvalidValue;
   const int ngroups = (N + imgs - 1) / imgs;
 #define LAUNCH(CI, CO, B)                                                                   \
   do {                                                                                      \
     auto kfn = fp8 ? conv_fwd_kernel<CI, CO, B, true> : conv_fwd_kernel<CI, CO, B, false>;  \
-    if (sm > 64 * 1024) hipFuncSetAttribute((const void*)kfn,                               \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); \
-    const int grid = fwd_grid(ngroups, (const void*)kfn, sm);                               \
+    const int grid = fwd_grid(ngroups, (const void*)kfn, sm); /* (raises the LDS limit) */  \
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(kThreads), sm, stream, a);                     \
   } while (0)
   // 17..32 pixels wide (config 4's 24 x 24), 16 channels: the WIDE row kernel
@@ -1868,16 +1842,17 @@ extern "C" int mbk_conv_fwd_fp8(const void* x, int in_bits, int cin, int cout, c
                          nullptr, N, H, W, imgs, relu_in, pool, true, stream);
 }
 
-#define WGRAD_DISPATCH(LAUNCH)                                                              \
+// LAUNCH(CI, CO, B) for the layer's (cin, cout, bit-plane input); ERR: returned for any other
+#define WGRAD_DISPATCH(LAUNCH, ERR)                                                         \
   if (in_bits) {                                                                            \
     if (cout == 16) LAUNCH(32, 16, true);                                                   \
     else if (cout == 32) LAUNCH(32, 32, true);                                              \
-    else return -(int)hipErrorInvalidValue;                                                 \
+    else return ERR;                                                                        \
   } else if (cin == 16 && cout == 16) LAUNCH(16, 16, false);                                \
   else if (cin == 16 && cout == 32) LAUNCH(16, 32, false);                                  \
   else if (cin == 32 && cout == 16) LAUNCH(32, 16, false);                                  \
   else if (cin == 32 && cout == 32) LAUNCH(32, 32, false);                                  \
-  else return -(int)hipErrorInvalidValue;
+  else return ERR;
 
 // the wgrad instantiation of (CI, CO, B) for this map width: band layout (WT = 8 / 16 / 24)
 // or the plain one; unpool: the stage-0 layer of a 16-wide map only (null otherwise)
@@ -1903,18 +1878,18 @@ static int occ_b2(int per) {  // twice the backward cap
 // number of partial rows mbk_conv_wgrad will write for this shape (<= nrounds)
 extern "C" int mbk_conv_wgrad_parts(int in_bits, int cin, int cout, int N, int H, int W,
                                     int imgs, int unpool) {
-  const size_t sm = wgrad_smem(cin, cout, imgs, H, W, unpool != 0);
+  const size_t sm = wgrad_smem(cin, cout, imgs, H, W);
   if (sm > 160 * 1024 || !index_math_ok(imgs, H, W)) return -(int)hipErrorInvalidValue;
   const int nrounds = (N + imgs - 1) / imgs;
-  int res = 1;
   const void* kq = nullptr;
 #define Q(CI, CO, B) kq = wgrad_kfn<CI, CO, B>(H, W, unpool != 0)
-  WGRAD_DISPATCH(Q)
+  WGRAD_DISPATCH(Q, -(int)hipErrorInvalidValue)
 #undef Q
   if (!kq) return -(int)hipErrorInvalidValue;
   // the backward cap leaves room for one acting workgroup (80 KB of LDS) beside the learner's:
   // a pool-fused stage-0 form small enough for two of its workgroups beside it may take two
-  res = resident_blocks(kq, sm, unpool != 0 && 2 * sm + 80 * 1024 <= 160 * 1024 ? occ_b2 : mbk_occ_b);
+  const int res = capped_resident_blocks(
+      kq, kThreads, sm, unpool != 0 && 2 * sm + 80 * 1024 <= 160 * 1024 ? occ_b2 : mbk_occ_b);
   return (int)std::max(1L, std::min((long)nrounds, (long)res));
 }
 
@@ -1930,28 +1905,20 @@ extern "C" int mbk_conv_wgrad(const void* x, int in_bits, int cin, int cout, con
 #define MBK_WGRAD_QUEUE 1  // build knob (tools/variant.py): 0 = static stride (A/B)
 #endif
   if (MBK_WGRAD_QUEUE) a.queue = mbk_work_queue(stream, kQueueWgrad);
-  const size_t sm = wgrad_smem(cin, cout, imgs, H, W, unpool);
+  const size_t sm = wgrad_smem(cin, cout, imgs, H, W);
   if (sm > 160 * 1024 || nparts < 1 || !index_math_ok(imgs, H, W))
     return (int)hipErrorInvalidValue;
   dim3 grid(nparts);
 #define LAUNCH(CI, CO, B)                                                                   \
   do {                                                                                      \
-    const void* kfn = wgrad_kfn<CI, CO, B>(H, W, unpool);                    \
-    if (!kfn) return (int)hipErrorInvalidValue;                              \
+    const void* kfn = wgrad_kfn<CI, CO, B>(H, W, unpool);                                   \
+    if (!kfn) return (int)hipErrorInvalidValue;                                             \
     if (sm > 64 * 1024)                                                                     \
       hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);        \
     void* args[] = {&a};                                                                    \
     hipLaunchKernel(kfn, grid, dim3(kThreads), args, sm, stream);                           \
   } while (0)
-  if (in_bits) {
-    if (cout == 16) LAUNCH(32, 16, true);
-    else if (cout == 32) LAUNCH(32, 32, true);
-    else return (int)hipErrorInvalidValue;
-  } else if (cin == 16 && cout == 16) LAUNCH(16, 16, false);
-  else if (cin == 16 && cout == 32) LAUNCH(16, 32, false);
-  else if (cin == 32 && cout == 16) LAUNCH(32, 16, false);
-  else if (cin == 32 && cout == 32) LAUNCH(32, 32, false);
-  else return (int)hipErrorInvalidValue;
+  WGRAD_DISPATCH(LAUNCH, (int)hipErrorInvalidValue)
 #undef LAUNCH
   return (int)hipGetLastError();
 }
@@ -1961,7 +1928,8 @@ extern "C" int mbk_conv_wgrad(const void* x, int in_bits, int cin, int cout, con
 // Two workgroups per unit of the backward cap, as the dense pool-fused form above.
 extern "C" int mbk_conv_wgrad0_sparse_parts(int N) {
   if (N < 1) return -(int)hipErrorInvalidValue;
-  const int res = resident_blocks((const void*)wgrad0_sparse_kernel, kS0Smem, occ_b2, kS0Threads);
+  const int res =
+      capped_resident_blocks((const void*)wgrad0_sparse_kernel, kS0Threads, kS0Smem, occ_b2);
   return (int)std::max(1L, std::min((long)(N + kS0Waves - 1) / kS0Waves, (long)res));
 }
 
@@ -1981,27 +1949,13 @@ extern "C" int mbk_conv_wgrad0_sparse(const void* x, const void* dp, const void*
 extern "C" void mbk_conv_set_grid_cap(int cap) { g_grid_cap = cap; }
 extern "C" void mbk_conv0_row_set(int on) { g_conv0_row = on; }
 
-// partial holds nparts rows plus ceil(nparts / kReducePps) scratch rows after them
-extern "C" int mbk_wgrad_reduce(const float* partial, int nparts, int cin, int cin_real, int cout,
-                                float* dw, float* db, int accumulate, hipStream_t stream) {
-  const int row = cout * 9 * cin + cout;
-  const dim3 cols((row + 63) / 64);
-  if (nparts > 2 * kReducePps) {
-    const int splits = (nparts + kReducePps - 1) / kReducePps;
-    float* stage = (float*)partial + (size_t)nparts * row;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cols.x, splits), dim3(256), 0, stream, partial,
-                       nparts, kReducePps, stage, cin, cin_real, cout, dw, db, accumulate);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cols.x, 1), dim3(256), 0, stream,
-                       (const float*)stage, splits, splits, (float*)nullptr, cin, cin_real, cout,
-                       dw, db, accumulate);
-  } else {
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cols.x, 1), dim3(256), 0, stream, partial,
-                       nparts, nparts, (float*)nullptr, cin, cin_real, cout, dw, db, accumulate);
-  }
-  return (int)hipGetLastError();
+// floats of one layer's partial-row buffer (launch.h: every caller sizes its buffer by this)
+extern "C" int64_t mbk_wgrad_partial_floats(int nparts, int cin, int cout) {
+  return wgrad_partial_floats(nparts, cin, cout);
 }
 
-// jobs[0..n): each as one mbk_wgrad_reduce call, in <= 2 launches per 32 jobs.
+// jobs[0..n): each job's nparts partial rows summed into its dw / db (overwritten), in <= 2
+// launches per 32 jobs. A job's buffer holds mbk_wgrad_partial_floats floats.
 extern "C" int mbk_wgrad_reduce_batch(const MbkReduceJob* jobs, int n, hipStream_t stream) {
   for (int j0 = 0; j0 < n; j0 += kMaxReduceJobs) {
     const int nj = std::min(kMaxReduceJobs, n - j0);
@@ -2013,11 +1967,10 @@ extern "C" int mbk_wgrad_reduce_batch(const MbkReduceJob* jobs, int n, hipStream
       if (!J.partial || !J.dw || J.nparts < 1 || J.cin < 1 || J.cout < 1 || J.cin_real > J.cin)
         return (int)hipErrorInvalidValue;
       b.j[i] = J;
-      const int row = J.cout * 9 * J.cin + J.cout;
-      cols = std::max(cols, (row + 63) / 64);
+      cols = std::max(cols, (wgrad_row_floats(J.cin, J.cout) + 63) / 64);
       if (J.nparts > 2 * kReducePps) {
         two = true;
-        splits = std::max(splits, (J.nparts + kReducePps - 1) / kReducePps);
+        splits = std::max(splits, wgrad_reduce_splits(J.nparts));
       }
     }
     hipLaunchKernelGGL(wgrad_reduce_batch_kernel, dim3(cols, splits, nj), dim3(256), 0, stream,

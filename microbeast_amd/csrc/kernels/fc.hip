@@ -9,6 +9,7 @@
 // both operands are staged row-major in LDS and read K-major with ds_read_b64_tr_b16,
 // fp32 partials are reduced by a deterministic two-level column sum. No host sync.
 #include "common.h"
+#include "launch.h"
 
 #include <cstdlib>
 
@@ -526,13 +527,7 @@ extern "C" int mbk_fc_fwd(const void* x, int relu_in, const void* w5, const floa
   if (I % 32) return (int)hipErrorInvalidValue;
   const int blocks = (F + 15) / 16;
   if ((O == 256 || O == 128) && I <= 128) {
-    static int cus = 0;
-    if (!cus) {
-      int dev = 0;
-      (void)hipGetDevice(&dev);
-      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-      if (cus <= 0) cus = 256;
-    }
+    const int cus = mbk::cu_count();
     const int grid = std::min((blocks + 1) / 2, cus * 2);  // 32-row groups; 2 workgroups per CU
 #define FC_RB(OO, KS)                                                                        \
   hipLaunchKernelGGL((fc_fwd_rb_kernel<OO, KS>), dim3(grid), dim3(256), 0, stream,          \
@@ -619,13 +614,7 @@ extern "C" int mbk_fc_wgrad(const void* g, const void* x, int N, int O, int I, f
 // 0: the shape (O = 256, I in {32, 64, 128}) is not covered
 extern "C" int mbk_fc_wgrad_wide_parts(int N, int O, int I) {
   if (O != 256 || (I != 32 && I != 64 && I != 128) || N <= 0) return 0;
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipGetDevice(&dev);
-    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
-  }
+  const int cus = mbk::cu_count();
   const int nst = (N + FW_RS - 1) / FW_RS;
   return std::max(1, std::min(cus, (nst + 3) / 4));
 }

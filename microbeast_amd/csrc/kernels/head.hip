@@ -34,6 +34,7 @@
 #include "../include/mbk_api.h"
 #include "../include/microrts_rules.h"
 #include "common.h"
+#include "launch.h"
 
 #ifndef MBK_HA_MB
 #define MBK_HA_MB 4
@@ -1676,13 +1677,11 @@ extern "C" int mbk_head_bwd(const void* X, const void* Wp, const void* WpT, cons
                             hipStream_t stream) {
   int bwd_grid = 1;
   {
-    static int cus = 0;
+    const int cus = mbk::cu_count();
     static uint64_t* hb_stamps = nullptr;
-    if (!cus) {
-      int dev = 0;
-      hipGetDevice(&dev);
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-      if (cus <= 0) cus = 256;
+    static bool init = false;
+    if (!init) {
+      init = true;
       hipFuncSetAttribute((const void*)head_bwd2_kernel<false>,
                           hipFuncAttributeMaxDynamicSharedMemorySize, HB_LDS);
       hipFuncSetAttribute((const void*)head_bwd2_kernel<true>,
@@ -1734,12 +1733,10 @@ extern "C" int mbk_head_score(const void* X, const void* Wp, const float* bp,
                               const int* grp_start, const int* grp_count, const int* chunk_cell,
                               const int* chunk_row, const int* totals, int S, float* plp,
                               float* pent, float* stats, hipStream_t stream) {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipGetDevice(&dev);
-    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
+  const int cus = mbk::cu_count();
+  static bool init = false;
+  if (!init) {
+    init = true;
     hipFuncSetAttribute((const void*)head_score_kernel,
                         hipFuncAttributeMaxDynamicSharedMemorySize, HS_LDS);
   }
@@ -1758,13 +1755,7 @@ extern "C" int mbk_head_dx_gather(const void* dXp, const int* pidx, const uint32
 
 // partial rows mbk_head_dx_value writes ([parts][257] fp32)
 extern "C" int mbk_head_dx_value_parts(int R) {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
-  }
+  const int cus = mbk::cu_count();
   const int need = (R + 3) / 4;
   return need < 1 ? 1 : (need < cus * 4 ? need : cus * 4);
 }
@@ -1819,13 +1810,7 @@ extern "C" int mbk_act_head(const MbkActModel* m, const MbkActStep* s, hipStream
   a.step = s->step;
   a.S = S;
   a.E = m->E;
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipGetDevice(&dev);
-    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
-  }
+  const int cus = mbk::cu_count();
   // three 2-wave workgroups per CU (the LDS logit tiles allow three): ~1500 waves for the
   // ~800 64-pair jobs of a settled 8192-env step
   hipLaunchKernelGGL(s->greedy ? head_act_greedy_kernel : head_act_kernel,

@@ -10,6 +10,7 @@
 #include "../include/mbk_api.h"
 #include "../include/microrts_rules.h"
 #include "common.h"
+#include "launch.h"
 #include "decode.h"
 
 namespace {
@@ -152,20 +153,9 @@ __global__ __launch_bounds__(512) void decode_obs_mask_kernel(const uint16_t* __
   }
 }
 
-int device_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
-  }
-  return cus;
-}
-
 int decode_grid(int E) {
   const int ngroups = (E + kEnvsPerWG - 1) / kEnvsPerWG;
-  return max(1, min(ngroups, device_cus() * 8));  // 8 resident 256-thread workgroups per CU
+  return max(1, min(ngroups, mbk::cu_count() * 8));  // 8 resident 256-thread workgroups per CU
 }
 
 int bucket_grid(int E) {

@@ -29,6 +29,7 @@
 //
 // All shapes are checked on the host (mbk_pconv_* return hipErrorInvalidValue).
 #include "common.h"
+#include "launch.h"
 
 #include <algorithm>
 
@@ -1470,8 +1471,7 @@ extern "C" int mbk_imgconv(const long long* v, int H, hipStream_t st) {
   if (a.a_bs % 8 || a.a_ps % 8 || a.c_bs % 8 || a.c_ps % 8 || ((uintptr_t)a.A & 15) ||
       ((uintptr_t)a.B & 15) || ((uintptr_t)a.C & 15) || ((uintptr_t)a.mask & 15))
     return (int)hipErrorInvalidValue;
-  int dev = 0, ncu = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+  const int ncu = mbk::cu_count();
 #define MBK_IC(CI, NO, HH)                                                                       \
   do {                                                                                           \
     using S = ImgCfg<CI, NO, HH>;                                                                \
@@ -1604,8 +1604,7 @@ extern "C" int mbk_rows_colsum(const void* Z, int ld, int C, const int* totals, 
 // (pixel stride, image stride); nparts = grid; partial [nparts][9][O][I]); supported
 // (I, O, H) = (32, 64, 8)
 extern "C" int mbk_imgwgrad_parts() {
-  int dev = 0, ncu = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+  const int ncu = mbk::cu_count();
   return 2 * ncu;
 }
 extern "C" int mbk_imgwgrad(const long long* v, int H, hipStream_t st) {

@@ -18,9 +18,10 @@
 //   wgrad : A = dY (16 co x 32 pixels) and B = X taps (32 pixels x 16 ci), both read with
 //           ds_read_b64_tr_b16 from the same halo'd tiles; acc over the 9 taps.
 // Weight grads go out as per-workgroup fp32 partial rows [2][16*144 + 16] reduced by
-// conv.hip's deterministic wgrad_reduce (bias grads included).
+// conv.hip's deterministic batched reduce (bias grads included).
 #include "../include/mbk_api.h"
 #include "common.h"
+#include "launch.h"
 
 #include <algorithm>
 
@@ -30,10 +31,6 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __hip_bfloat16 bf16;
-
-extern "C" int mbk_wgrad_reduce(const float* partial, int nparts, int cin, int cin_real,
-                                int cout, float* dw, float* db, int accumulate,
-                                hipStream_t stream);
 
 namespace {
 
@@ -693,23 +690,12 @@ bool res_bwd_w88(int H, int W) { return H == 8 && W == 8; }
 int res_grid(int N, int H, int W, int imgs) {
   if (res_bwd_w88(H, W)) imgs = w88b::NP;  // NP wave pairs, an image each
   const size_t sm = res_bwd_w88(H, W) ? res_w88b_smem() : res_smem(imgs, H, W);
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
-  }
-  const int ncu = cus;
   const void* kfn = res_bwd_w88(H, W) ? (const void*)res_bwd16_w88_kernel
                                        : (const void*)res_bwd16_kernel<0>;  // (every width)
-  if (sm > 64 * 1024) (void)hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-  int per = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kfn, res_bwd_w88(H, W) ? w88b::kPT : kThreads,
-                                                   sm) != hipSuccess || per < 1)
-    per = 1;
+  const int res =
+      mbk::resident_blocks(kfn, res_bwd_w88(H, W) ? w88b::kPT : kThreads, sm, mbk_occ_b);
   const int nrounds = (N + imgs - 1) / imgs;
-  return (int)std::max(1L, std::min((long)nrounds, (long)ncu * mbk_occ_b(per)));
+  return std::max(1, std::min(nrounds, res));
 }
 
 }  // namespace
@@ -1943,47 +1929,25 @@ static int res_fwd16_launch(ResFwdArgs a, hipStream_t stream) {
                 : (W == 8 ? res_fwd16_kernel<8, false> : W == 5 ? res_fwd16_kernel<5, false>
                    : W == 12 ? res_fwd16_kernel<12, false> : W == 4 ? res_fwd16_kernel<4, false>
                    : res_fwd16_kernel<0, false>);
-  if (smf > 64 * 1024) (void)hipFuncSetAttribute((const void*)kfn,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)smf);
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
-  }
-  const int ncu = cus;
-  int per = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void*)kfn, kThreads, smf) !=
-          hipSuccess || per < 1)
-    per = 1;
+  const int res = mbk::resident_blocks((const void*)kfn, kThreads, smf, mbk_occ_f);
   // work items: images per wave (wave-owned) or rounds of imgs images per workgroup
   const int nrounds = fast ? (N + kThreads / 64 - 1) / (kThreads / 64) : (N + imgs - 1) / imgs;
-  hipLaunchKernelGGL(kfn, dim3(std::max(1L, std::min((long)nrounds, (long)ncu * mbk_occ_f(per)))),
-                     dim3(kThreads), smf, stream, a);
+  hipLaunchKernelGGL(kfn, dim3(std::max(1, std::min(nrounds, res))), dim3(kThreads), smf, stream,
+                     a);
   return (int)hipGetLastError();
 }
 
-// floats mbk_res_bwd16 needs in ``partial``: per layer, nparts rows + the two-level
-// reduce's scratch rows (conv.hip wgrad_reduce stages its split sums after the rows)
-extern "C" int64_t mbk_res_bwd16_partial_floats(int nparts) {
-  return 2 * (int64_t)(nparts + (nparts + 31) / 32) * ROW;
-}
-
-// dx = conv0^T(conv1^T(g) * [u>0]) * [x>0] + g and both layers' weight / bias gradients.
-// partial: mbk_res_bwd16_partial_floats(nparts) floats. dw1/db1/dw0/db0: fp32 parameter
-// gradients [16][16][3][3] / [16] (overwritten); dw1 == nullptr: only the partial rows are
-// written (layer 1's at partial, layer 0's at partial + partial_floats / 2) and the caller
-// reduces them later.
+// dx = conv0^T(conv1^T(g) * [u>0]) * [x>0] + g and both layers' partial rows of weight / bias
+// gradients: conv1's at partial, conv0's one layer buffer (launch.h wgrad_partial_floats)
+// after them; the caller reduces them (mbk_wgrad_reduce_batch).
 extern "C" int mbk_res_bwd16(const void* x, const void* u, const void* g, void* dx,
                              const void* w1t, const void* w0t, float* partial, int nparts,
-                             float* dw1, float* db1, float* dw0, float* db0, int N, int H, int W,
-                             int imgs, int accumulate, hipStream_t stream) {
+                             int N, int H, int W, int imgs, hipStream_t stream) {
   if (N <= 0) return 0;
   if (nparts < 1 || nparts != mbk_res_bwd16_parts(N, H, W, imgs)) return (int)hipErrorInvalidValue;
   const bool fast = res_bwd_w88(H, W);
   const size_t sm = fast ? res_w88b_smem() : res_smem(imgs, H, W);
-  const int64_t lstride = (int64_t)(nparts + (nparts + 31) / 32) * ROW;
+  const int64_t lstride = mbk::wgrad_partial_floats(nparts, C, C);
   ResBwdArgs a{(const bf16*)x, (const bf16*)u, (const bf16*)g, (bf16*)dx,
                (const bf16*)w1t, (const bf16*)w0t, partial, lstride, N, H, W, imgs};
   auto kfn = fast ? res_bwd16_w88_kernel : W == 5 ? res_bwd16_kernel<5>
@@ -1991,11 +1955,7 @@ extern "C" int mbk_res_bwd16(const void* x, const void* u, const void* g, void* 
   if (sm > 64 * 1024) (void)hipFuncSetAttribute((const void*)kfn,
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
   hipLaunchKernelGGL(kfn, dim3(nparts), dim3(fast ? w88b::kPT : kThreads), sm, stream, a);
-  int rc = (int)hipGetLastError();
-  if (rc || !dw1) return rc;  // dw1 == nullptr: the caller reduces (mbk_wgrad_reduce_batch)
-  rc = mbk_wgrad_reduce(partial, nparts, C, C, C, dw1, db1, accumulate, stream);
-  if (rc) return rc;
-  return mbk_wgrad_reduce(partial + lstride, nparts, C, C, C, dw0, db0, accumulate, stream);
+  return (int)hipGetLastError();
 }
 
 // Partial-row PAIRS mbk_res_bwd32 writes (= its grid: one 8-wave workgroup per CU);
@@ -2004,46 +1964,28 @@ extern "C" int mbk_res_bwd32_parts(int N, int H, int W, int imgs) {
   if (N <= 0 || imgs < 1 || H * W > 1024 || (int64_t)imgs * H * W >= (int64_t(1) << 22))
     return -1;
   if (res32b_smem(imgs, H, W) > 160 * 1024) return -1;
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
-  }
-  const int ncu = cus;
   const int nrounds = (N + imgs - 1) / imgs;
-  return std::max(1, std::min(nrounds, ncu));
+  return std::max(1, std::min(nrounds, mbk::cu_count()));
 }
 
 // Partial-row PAIRS mbk_res_bwd32_team writes (teams of its grid); <= 0: unsupported shape.
 extern "C" int mbk_res_bwd32_team_parts(int N, int H, int W) {
   if (N <= 0 || H != W || (W != 4 && W != 2)) return -1;
-  static int cus = 0, per4 = 0, per2 = 0;
-  if (!cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
-    (void)hipFuncSetAttribute((const void*)res_bwd32_team_kernel<4>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, rbt::smem<4>());
-    (void)hipFuncSetAttribute((const void*)res_bwd32_team_kernel<2>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, rbt::smem<2>());
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per4, (const void*)res_bwd32_team_kernel<4>,
-                                                     rbt::kPT, rbt::smem<4>()) != hipSuccess || per4 < 1)
-      per4 = 1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per2, (const void*)res_bwd32_team_kernel<2>,
-                                                     rbt::kPT, rbt::smem<2>()) != hipSuccess || per2 < 1)
-      per2 = 1;
-  }
+  // (one occupancy query per kernel, not per launch)
+  static const int per4 = mbk::blocks_per_cu((const void*)res_bwd32_team_kernel<4>, rbt::kPT,
+                                             rbt::smem<4>());
+  static const int per2 = mbk::blocks_per_cu((const void*)res_bwd32_team_kernel<2>, rbt::kPT,
+                                             rbt::smem<2>());
   const int64_t nitems = ((int64_t)N * H * W + 31) / 32;
   const int64_t wgs = (nitems + rbt::NT - 1) / rbt::NT;
-  return (int)(rbt::NT * std::max<int64_t>(1, std::min<int64_t>(wgs, (int64_t)cus * mbk_occ_b(W == 4 ? per4 : per2))));
+  const int res = mbk::resident_blocks(W == 4 ? per4 : per2, mbk_occ_b);
+  return (int)(rbt::NT * std::max<int64_t>(1, std::min<int64_t>(wgs, res)));
 }
 
 // The 32-channel block backward on 4x4 / 2x2 maps by wave teams (res_bwd32_team_kernel):
 // dx (bit-identical to mbk_res_bwd32) and the two layers' partial rows (conv1 at partial,
-// conv0 at partial + partial_floats / 2); the caller reduces them (mbk_wgrad_reduce_batch).
+// conv0 one layer buffer after them, as mbk_res_bwd16); the caller reduces them
+// (mbk_wgrad_reduce_batch).
 extern "C" int mbk_res_bwd32_team(const void* x, const void* u, const void* g, void* dx,
                                   const void* w1t, const void* w0t, float* partial, int nparts,
                                   int N, int H, int W, hipStream_t stream) {
@@ -2052,7 +1994,7 @@ extern "C" int mbk_res_bwd32_team(const void* x, const void* u, const void* g, v
   if ((((uintptr_t)x | (uintptr_t)u | (uintptr_t)g | (uintptr_t)w1t | (uintptr_t)w0t) & 15) ||
       ((uintptr_t)dx & 7))
     return (int)hipErrorInvalidValue;
-  const int64_t lstride = (int64_t)(nparts + (nparts + 31) / 32) * ROW32;
+  const int64_t lstride = mbk::wgrad_partial_floats(nparts, C32, C32);
   ResBwd32Args a{(const bf16*)x, (const bf16*)u, (const bf16*)g, (bf16*)dx,
                  (const bf16*)w1t, (const bf16*)w0t, partial, lstride, N, H, W, 1};
   const void* kfn = W == 4 ? (const void*)res_bwd32_team_kernel<4> : (const void*)res_bwd32_team_kernel<2>;
@@ -2062,21 +2004,15 @@ extern "C" int mbk_res_bwd32_team(const void* x, const void* u, const void* g, v
   return (int)hipGetLastError();
 }
 
-extern "C" int64_t mbk_res_bwd32_partial_floats(int nparts) {
-  return 2 * (int64_t)(nparts + (nparts + 31) / 32) * ROW32;
-}
-
-// 32-channel block backward (see res_bwd32_kernel): dx and both layers' weight / bias
-// gradients dw1/db1/dw0/db0 (fp32 [32][32][3][3] / [32], overwritten; dw1 == nullptr: partial
-// rows only, as mbk_res_bwd16).
+// 32-channel block backward (see res_bwd32_kernel): dx and both layers' partial rows of
+// weight / bias gradients, laid out and reduced as mbk_res_bwd16's.
 extern "C" int mbk_res_bwd32(const void* x, const void* u, const void* g, void* dx,
                              const void* w1t, const void* w0t, float* partial, int nparts,
-                             float* dw1, float* db1, float* dw0, float* db0, int N, int H, int W,
-                             int imgs, int accumulate, hipStream_t stream) {
+                             int N, int H, int W, int imgs, hipStream_t stream) {
   if (N <= 0) return 0;
   if (nparts < 1 || nparts != mbk_res_bwd32_parts(N, H, W, imgs)) return (int)hipErrorInvalidValue;
   const size_t sm = res32b_smem(imgs, H, W);
-  const int64_t lstride = (int64_t)(nparts + (nparts + 31) / 32) * ROW32;
+  const int64_t lstride = mbk::wgrad_partial_floats(nparts, C32, C32);
   ResBwd32Args a{(const bf16*)x, (const bf16*)u, (const bf16*)g, (bf16*)dx,
                  (const bf16*)w1t, (const bf16*)w0t, partial, lstride, N, H, W, imgs};
   auto kfn = W == 4 ? res_bwd32_kernel<4> : W == 2 ? res_bwd32_kernel<2>
@@ -2085,11 +2021,7 @@ extern "C" int mbk_res_bwd32(const void* x, const void* u, const void* g, void* 
   if (sm > 64 * 1024) (void)hipFuncSetAttribute((const void*)kfn,
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
   hipLaunchKernelGGL(kfn, dim3(nparts), dim3(kT32), sm, stream, a);
-  int rc = (int)hipGetLastError();
-  if (rc || !dw1) return rc;  // dw1 == nullptr: the caller reduces (mbk_wgrad_reduce_batch)
-  rc = mbk_wgrad_reduce(partial, nparts, C32, C32, C32, dw1, db1, accumulate, stream);
-  if (rc) return rc;
-  return mbk_wgrad_reduce(partial + lstride, nparts, C32, C32, C32, dw0, db0, accumulate, stream);
+  return (int)hipGetLastError();
 }
 
 // One 32-channel residual block's forward (see res_blk32_kernel): u = conv0(relu x),
@@ -2105,25 +2037,18 @@ extern "C" int mbk_res_blk32_fwd_wave(const void* x, void* u, void* y, const voi
     return (int)hipErrorInvalidValue;
   const void* kfn = W == 4 ? (const void*)res_blk32_wave_kernel<4> : (const void*)res_blk32_wave_kernel<2>;
   const int sm = W == 4 ? rbw::smem<4>() : rbw::smem<2>();
-  static int cus = 0, per4 = 0, per2 = 0;
-  if (!cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per4, (const void*)res_blk32_wave_kernel<4>,
-                                                     rbw::kPT, rbw::smem<4>()) != hipSuccess || per4 < 1)
-      per4 = 1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per2, (const void*)res_blk32_wave_kernel<2>,
-                                                     rbw::kPT, rbw::smem<2>()) != hipSuccess || per2 < 1)
-      per2 = 1;
-  }
+  // (one occupancy query per kernel, not per launch)
+  static const int per4 = mbk::blocks_per_cu((const void*)res_blk32_wave_kernel<4>, rbw::kPT,
+                                             rbw::smem<4>());
+  static const int per2 = mbk::blocks_per_cu((const void*)res_blk32_wave_kernel<2>, rbw::kPT,
+                                             rbw::smem<2>());
   ResBlk32Args a{(const bf16*)x, (bf16*)u, (bf16*)y, {(const bf16*)w[0], (const bf16*)w[1]},
                  {b[0], b[1]}, N, H, W, 1};
   a.queue = mbk_work_queue(stream, kQueueBlk32);
   const int64_t nq = ((int64_t)N * H * W + 15) / 16;
   const int64_t groups = (nq + rbw::NW - 1) / rbw::NW;
-  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(groups, (int64_t)cus * mbk_occ_f(W == 4 ? per4 : per2)));
+  const int grid = (int)std::max<int64_t>(
+      1, std::min<int64_t>(groups, mbk::resident_blocks(W == 4 ? per4 : per2, mbk_occ_f)));
   void* args[] = {(void*)&a};
   (void)hipLaunchKernel(kfn, dim3(grid), dim3(rbw::kPT), args, sm, stream);
   return (int)hipGetLastError();
@@ -2142,22 +2067,8 @@ extern "C" int mbk_res_blk32_fwd(const void* x, void* u, void* y, const void* co
   auto kfn = W == 4 ? res_blk32_kernel<4> : W == 2 ? res_blk32_kernel<2>
            : W == 8 ? res_blk32_kernel<8> : W == 3 ? res_blk32_kernel<3>
            : W == 6 ? res_blk32_kernel<6> : res_blk32_kernel<0>;
-  if (sm > 64 * 1024) (void)hipFuncSetAttribute((const void*)kfn,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
-  }
-  const int ncu = cus;
-  int per = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void*)kfn, kThreads, sm) !=
-          hipSuccess || per < 1)
-    per = 1;
+  const int res = mbk::resident_blocks((const void*)kfn, kThreads, sm, mbk_occ_f);
   const int nrounds = (N + imgs - 1) / imgs;
-  hipLaunchKernelGGL(kfn, dim3(std::max(1, std::min(nrounds, ncu * mbk_occ_f(per)))), dim3(kThreads), sm,
-                     stream, a);
+  hipLaunchKernelGGL(kfn, dim3(std::max(1, std::min(nrounds, res))), dim3(kThreads), sm, stream, a);
   return (int)hipGetLastError();
 }

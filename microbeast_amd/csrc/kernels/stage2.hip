@@ -16,6 +16,7 @@
 //     strict > (the first maximising tap: mbk::pool_tile's values and argmax bytes).
 #include "../include/mbk_api.h"
 #include "common.h"
+#include "launch.h"
 
 #include <algorithm>
 
@@ -185,21 +186,13 @@ extern "C" int mbk_pool_conv_fwd4(const void* x, const void* w, const float* bia
   if (!x || !w || !bias || !y || (((uintptr_t)x | (uintptr_t)w) & 15) || ((uintptr_t)y & 7) ||
       ((uintptr_t)pidx & 3))
     return (int)hipErrorInvalidValue;
-  static int cus = 0, per = 0;
-  if (!cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void*)pool_conv_fwd4_kernel,
-                                                     s2::kPT, s2::SMEM) != hipSuccess || per < 1)
-      per = 1;
-  }
+  // (one occupancy query, not one per launch)
+  static const int per = mbk::blocks_per_cu((const void*)pool_conv_fwd4_kernel, s2::kPT, s2::SMEM);
   const int npairs = (N + s2::NI - 1) / s2::NI;
   const int groups = (npairs + s2::NW - 1) / s2::NW;
   PoolConvFwd4Args a{(const bf16*)x, (const bf16*)w, bias, (bf16*)y, (uint8_t*)pidx, N};
   a.queue = mbk_work_queue(stream, kQueuePoolConv4);
-  hipLaunchKernelGGL(pool_conv_fwd4_kernel, dim3(std::max(1, std::min(groups, cus * mbk_occ_f(per)))),
-                     dim3(s2::kPT), s2::SMEM, stream, a);
+  const int grid = std::max(1, std::min(groups, mbk::resident_blocks(per, mbk_occ_f)));
+  hipLaunchKernelGGL(pool_conv_fwd4_kernel, dim3(grid), dim3(s2::kPT), s2::SMEM, stream, a);
   return (int)hipGetLastError();
 }

@@ -28,6 +28,7 @@
 // one 32-pixel K block of the weight gradient.
 #include "../include/mbk_api.h"
 #include "common.h"
+#include "launch.h"
 
 #include <algorithm>
 
@@ -35,10 +36,6 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __hip_bfloat16 bf16;
-
-extern "C" int mbk_wgrad_reduce(const float* partial, int nparts, int cin, int cin_real,
-                                int cout, float* dw, float* db, int accumulate,
-                                hipStream_t stream);
 
 namespace {
 
@@ -455,34 +452,22 @@ static bool pool_conv_s2(int cin, int cout, int H, int W) {
 extern "C" int mbk_pool_conv_bwd_parts(int N, int cin, int cout, int H, int W) {
   const bool one = pool_conv_s1(cin, cout, H, W);
   if (N <= 0 || !(one || pool_conv_s2(cin, cout, H, W))) return -1;
-  static int cus = 0, per1 = 0, per2 = 0;
-  if (!cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
-    (void)hipFuncSetAttribute((const void*)pool_conv_bwd_s1_kernel,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, s1::SMEM);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per1, (const void*)pool_conv_bwd_s1_kernel,
-                                                     s1::kPT, s1::SMEM) != hipSuccess || per1 < 1)
-      per1 = 1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per2, (const void*)pool_conv_bwd_s2_kernel,
-                                                     s2::kPT, s2::SMEM) != hipSuccess || per2 < 1)
-      per2 = 1;
-  }
+  // (one occupancy query per kernel, not per launch)
+  static const int per1 =
+      mbk::blocks_per_cu((const void*)pool_conv_bwd_s1_kernel, s1::kPT, s1::SMEM);
+  static const int per2 =
+      mbk::blocks_per_cu((const void*)pool_conv_bwd_s2_kernel, s2::kPT, s2::SMEM);
   const int rounds = one ? (N + s1::NW - 1) / s1::NW
                          : ((N + s2::NI - 1) / s2::NI + s2::NW / 2 - 1) / (s2::NW / 2);
-  return std::max(1, std::min(rounds, cus * mbk_occ_b(one ? per1 : per2)));
+  return std::max(1, std::min(rounds, mbk::resident_blocks(one ? per1 : per2, mbk_occ_b)));
 }
 
-// dx = conv^T(pool_bwd(dp, pidx)) and the conv's weight / bias gradients (dw [cout][cin][3][3],
-// db [cout], fp32; accumulate: add instead of overwrite). partial:
-// mbk_pool_conv_bwd_partial_floats(nparts, cin, cout) floats (the rows plus the reduce's scratch
-// rows, conv.hip mbk_wgrad_reduce).
+// dx = conv^T(pool_bwd(dp, pidx)) and the conv's partial rows of weight / bias gradients:
+// partial holds launch.h's wgrad_partial_floats(nparts, cin, cout) floats (the rows plus the
+// reduce's scratch rows); the caller reduces them (mbk_wgrad_reduce_batch).
 extern "C" int mbk_pool_conv_bwd(const void* dp, const void* pidx, const void* x, const void* wt,
-                                 void* dx, float* partial, int nparts, float* dw, float* db,
-                                 int N, int cin, int cout, int H, int W, int accumulate,
-                                 hipStream_t stream) {
+                                 void* dx, float* partial, int nparts, int N, int cin, int cout,
+                                 int H, int W, hipStream_t stream) {
   if (N <= 0) return 0;
   if (nparts < 1 || nparts != mbk_pool_conv_bwd_parts(N, cin, cout, H, W))
     return (int)hipErrorInvalidValue;
@@ -495,11 +480,5 @@ extern "C" int mbk_pool_conv_bwd(const void* dp, const void* pidx, const void* x
     hipLaunchKernelGGL(pool_conv_bwd_s1_kernel, dim3(nparts), dim3(s1::kPT), s1::SMEM, stream, a);
   else
     hipLaunchKernelGGL(pool_conv_bwd_s2_kernel, dim3(nparts), dim3(s2::kPT), s2::SMEM, stream, a);
-  const int rc = (int)hipGetLastError();
-  if (rc || !dw) return rc;  // dw == nullptr: the caller reduces (mbk_wgrad_reduce_batch)
-  return mbk_wgrad_reduce(partial, nparts, cin, cin, cout, dw, db, accumulate, stream);
-}
-
-extern "C" int64_t mbk_pool_conv_bwd_partial_floats(int nparts, int cin, int cout) {
-  return (int64_t)(nparts + (nparts + 31) / 32) * (cout * 9 * cin + cout);
+  return (int)hipGetLastError();
 }

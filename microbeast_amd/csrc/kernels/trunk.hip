@@ -21,6 +21,7 @@
 // fp32 accumulation, pool over bf16-rounded values).
 #include "../include/mbk_api.h"
 #include "common.h"
+#include "launch.h"
 #include "decode.h"
 
 
@@ -1460,13 +1461,7 @@ static int trunk_launch(TrunkArgs a, int N, int H0, int W0, hipStream_t stream) 
   a.N = N;
   a.H0 = H0;
   a.W0 = W0;
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipGetDevice(&dev);
-    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
-  }
+  const int cus = mbk::cu_count();
   // images per iteration: as many as LDS allows (each conv phase pays one L2 round trip
   // for its weights, so more images amortise it) while keeping >= one group per CU
   const bool f8 = a.w8[0] != nullptr;
@@ -1577,13 +1572,7 @@ extern "C" int mbk_act_trunk(const MbkActModel* m, const MbkActStep* s, hipStrea
   a.reward_dst = s->reward_dst;
   a.done_dst = s->done_dst;
   a.stamps = g_act_stamps;
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipGetDevice(&dev);
-    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
-  }
+  const int cus = mbk::cu_count();
   const void* kfn = (const void*)act_trunk_w_kernel;
   static bool attr = false;
   if (!attr) {

@@ -44,7 +44,7 @@ class _Job(ctypes.Structure):
 class _RJob(ctypes.Structure):  # conv.hip MbkReduceJob
     _fields_ = [("partial", ctypes.c_void_p), ("dw", ctypes.c_void_p), ("db", ctypes.c_void_p),
                 ("nparts", ctypes.c_int), ("cin", ctypes.c_int), ("cin_real", ctypes.c_int),
-                ("cout", ctypes.c_int), ("accumulate", ctypes.c_int)]
+                ("cout", ctypes.c_int)]
 
 
 class _Job8(ctypes.Structure):
@@ -328,9 +328,7 @@ class HipEncoder:
                                                   int(dy is None))
         if nparts < 1:
             raise RuntimeError(f"conv_wgrad: unsupported shape {L}")
-        row = L.cout * 9 * L.cin + L.cout
-        need = (nparts + (nparts + 31) // 32) * row  # + the two-level reduce's scratch rows
-        part = self._partials(L, need, x.device)
+        part, _ = self._part_rows(L, nparts, 1, x.device)
         k = N.kernels()
         st = N.stream_ptr()
         N.check(k.mbk_conv_wgrad(x.data_ptr(), int(L.bits), L.cin, L.cout, N.ptr(dy),
@@ -346,9 +344,7 @@ class HipEncoder:
         nparts = k.mbk_conv_wgrad0_sparse_parts(n)
         if nparts < 1:
             raise RuntimeError(f"conv_wgrad0_sparse: unsupported batch {n}")
-        row = L.cout * 9 * L.cin + L.cout
-        need = (nparts + (nparts + 31) // 32) * row  # + the two-level reduce's scratch rows
-        part = self._partials(L, need, x.device)
+        part, _ = self._part_rows(L, nparts, 1, x.device)
         N.check(k.mbk_conv_wgrad0_sparse(x.data_ptr(), dp.data_ptr(), pidx.data_ptr(), EMPTY_WORD,
                                          part.data_ptr(), nparts, n, N.stream_ptr()),
                 "conv_wgrad0_sparse")
@@ -363,10 +359,17 @@ class HipEncoder:
             self._pbufs[key] = b
         return b
 
+    def _part_rows(self, L: ConvLayer, nparts: int, layers: int, device):
+        """The partial-row buffer for ``layers`` layers of L's shape (L's own buffer), nparts
+        rows each, and the floats from one layer's rows to the next's: the rows plus the
+        reduce's scratch rows (launch.h)."""
+        stride = N.kernels().mbk_wgrad_partial_floats(nparts, L.cin, L.cout)
+        return self._partials(L, layers * stride, device), stride
+
     def _reduce(self, partial: int, nparts: int, L: ConvLayer, dw, db) -> None:
         """Sum nparts partial rows at ``partial`` into L's fp32 dw / db: now, or queued for the
         backward pass's one batched launch (bit-identical either way, conv.hip)."""
-        job = _RJob(partial, dw.data_ptr(), db.data_ptr(), nparts, L.cin, L.cin_real, L.cout, 0)
+        job = _RJob(partial, dw.data_ptr(), db.data_ptr(), nparts, L.cin, L.cin_real, L.cout)
         if self._rjobs is not None:
             self._rjobs.append(job)
             return
@@ -454,14 +457,12 @@ class HipEncoder:
         nparts = k.mbk_res_bwd16_parts(n, H, W, imgs)
         if nparts < 1:
             raise RuntimeError(f"res_bwd16: unsupported shape {H}x{W}")
-        need = k.mbk_res_bwd16_partial_floats(nparts)
-        part = self._partials(L0, need, x.device)
+        part, stride = self._part_rows(L0, nparts, 2, x.device)
         N.check(k.mbk_res_bwd16(x.data_ptr(), u.data_ptr(), g.data_ptr(), dx.data_ptr(),
                                 base + 2 * L1.wb_off, base + 2 * L0.wb_off, part.data_ptr(),
-                                nparts, None, None, None, None, n, H, W, imgs, 0,
-                                N.stream_ptr()), "res_bwd16")
+                                nparts, n, H, W, imgs, N.stream_ptr()), "res_bwd16")
         self._reduce(part.data_ptr(), nparts, L1, dw1, db1)
-        self._reduce(part.data_ptr() + 4 * (need // 2), nparts, L0, dw0, db0)
+        self._reduce(part.data_ptr() + 4 * stride, nparts, L0, dw0, db0)
         return dx
 
     def _pool_conv_bwd(self, L: ConvLayer, dp, pidx, x, dw, db):
@@ -470,13 +471,12 @@ class HipEncoder:
         n = x.shape[0]
         k = N.kernels()
         nparts = k.mbk_pool_conv_bwd_parts(n, L.cin, L.cout, L.H, L.W)
-        need = k.mbk_pool_conv_bwd_partial_floats(nparts, L.cin, L.cout)
-        part = self._partials(L, need, x.device)
+        part, _ = self._part_rows(L, nparts, 1, x.device)
         dx = torch.empty_like(x)
         N.check(k.mbk_pool_conv_bwd(dp.data_ptr(), pidx.data_ptr(), x.data_ptr(),
                                     self.packed_bwd.data_ptr() + 2 * L.wb_off, dx.data_ptr(),
-                                    part.data_ptr(), nparts, None, None, n, L.cin, L.cout, L.H,
-                                    L.W, 0, N.stream_ptr()), "pool_conv_bwd")
+                                    part.data_ptr(), nparts, n, L.cin, L.cout, L.H, L.W,
+                                    N.stream_ptr()), "pool_conv_bwd")
         self._reduce(part.data_ptr(), nparts, L, dw, db)
         return dx
 
@@ -488,33 +488,23 @@ class HipEncoder:
         k = N.kernels()
         if self.fused_res_bwd32_team and H == W and W in (2, 4):
             # wave teams on 32-pixel items, no workgroup barriers (resblock.hip)
-            dx = torch.empty_like(x)
-            base = self.packed_bwd.data_ptr()
+            name, fn, tail = "res_bwd32_team", k.mbk_res_bwd32_team, ()
             nparts = k.mbk_res_bwd32_team_parts(n, H, W)
-            need = k.mbk_res_bwd32_partial_floats(nparts)
-            part = self._partials(L0, need, x.device)
-            N.check(k.mbk_res_bwd32_team(x.data_ptr(), u.data_ptr(), g.data_ptr(), dx.data_ptr(),
-                                         base + 2 * L1.wb_off, base + 2 * L0.wb_off,
-                                         part.data_ptr(), nparts, n, H, W, N.stream_ptr()),
-                    "res_bwd32_team")
-            self._reduce(part.data_ptr(), nparts, L1, dw1, db1)
-            self._reduce(part.data_ptr() + 4 * (need // 2), nparts, L0, dw0, db0)
-            return dx
-        lds_kb = _RES32_LDS_KB if H * W > 4 else _RES32_LDS_KB_SMALL
-        imgs = max(1, min(_RES32_PIX // (H * W), (lds_kb * 1024 - 128) // (4 * (H + 2) * (W + 2) * 80)))
+        else:
+            lds_kb = _RES32_LDS_KB if H * W > 4 else _RES32_LDS_KB_SMALL
+            imgs = max(1, min(_RES32_PIX // (H * W), (lds_kb * 1024 - 128) // (4 * (H + 2) * (W + 2) * 80)))
+            name, fn, tail = "res_bwd32", k.mbk_res_bwd32, (imgs,)
+            nparts = k.mbk_res_bwd32_parts(n, H, W, imgs)
+            if nparts < 1:
+                raise RuntimeError(f"res_bwd32: unsupported shape {H}x{W}")
         dx = torch.empty_like(x)
         base = self.packed_bwd.data_ptr()
-        nparts = k.mbk_res_bwd32_parts(n, H, W, imgs)
-        if nparts < 1:
-            raise RuntimeError(f"res_bwd32: unsupported shape {H}x{W}")
-        need = k.mbk_res_bwd32_partial_floats(nparts)
-        part = self._partials(L0, need, x.device)
-        N.check(k.mbk_res_bwd32(x.data_ptr(), u.data_ptr(), g.data_ptr(), dx.data_ptr(),
-                                base + 2 * L1.wb_off, base + 2 * L0.wb_off, part.data_ptr(),
-                                nparts, None, None, None, None, n, H, W, imgs, 0,
-                                N.stream_ptr()), "res_bwd32")
+        part, stride = self._part_rows(L0, nparts, 2, x.device)
+        N.check(fn(x.data_ptr(), u.data_ptr(), g.data_ptr(), dx.data_ptr(), base + 2 * L1.wb_off,
+                   base + 2 * L0.wb_off, part.data_ptr(), nparts, n, H, W, *tail, N.stream_ptr()),
+                name)
         self._reduce(part.data_ptr(), nparts, L1, dw1, db1)
-        self._reduce(part.data_ptr() + 4 * (need // 2), nparts, L0, dw0, db0)
+        self._reduce(part.data_ptr() + 4 * stride, nparts, L0, dw0, db0)
         return dx
 
     # ------------------------------------------------------------ passes
