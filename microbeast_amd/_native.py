@@ -79,15 +79,21 @@ _SIGS = {
     "mbk_to_bf16": [c_void_p, c_int64, c_void_p, c_void_p],
     "mbk_from_bf16": [c_void_p, c_int64, c_void_p, c_void_p],
     "mbk_conv_fwd": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                     c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                     c_void_p],
+                     c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "mbk_conv_fwd_fp8": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                         c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+                         c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    # images per workgroup round the launchers choose (pure arithmetic: no device needed)
+    "mbk_conv_fwd_imgs": [c_int, c_int, c_int, c_int, c_int, c_int, c_int],
+    "mbk_conv_wgrad_imgs": [c_int, c_int, c_int, c_int, c_int, c_int],
+    "mbk_res_bwd16_imgs": [c_int, c_int],
+    "mbk_res_blk32_fwd_imgs": [c_int, c_int],
+    "mbk_res_bwd32_imgs": [c_int, c_int],
+    "mbk_res_fwd16_stage_ok": [c_int, c_int],
     "mbk_conv_pack_fp8": [c_void_p, c_int, c_void_p],
     "mbk_pool_bwd_idx": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "mbk_conv_wgrad": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                        c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    "mbk_conv_wgrad_parts": [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int],
+    "mbk_conv_wgrad_parts": [c_int, c_int, c_int, c_int, c_int, c_int, c_int],
     "mbk_conv_wgrad0_sparse_parts": [c_int],
     "mbk_conv_wgrad0_sparse": [c_void_p, c_void_p, c_void_p, ctypes.c_uint, c_void_p, c_int, c_int,
                                c_void_p],
@@ -149,16 +155,15 @@ _SIGS = {
     "mbk_trunk_tail_fc": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                           c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
     "mbk_pack_env_actions": [c_void_p, c_int64, c_void_p, c_void_p],
-    "mbk_res_bwd16_parts": [c_int, c_int, c_int, c_int],
-    "mbk_res_bwd32_parts": [c_int, c_int, c_int, c_int],
+    "mbk_res_bwd16_parts": [c_int, c_int, c_int],
+    "mbk_res_bwd32_parts": [c_int, c_int, c_int],
     "mbk_res_bwd32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                      c_int, c_int, c_int, c_int, c_void_p],
-    "mbk_res_fwd16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                       c_int, c_int, c_int, c_void_p],
+    "mbk_res_fwd16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                      c_int, c_int, c_void_p],
     "mbk_res_fwd16_stage": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                            c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                            c_void_p],
-    "mbk_res_blk32_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                            c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
+    "mbk_res_blk32_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                           c_void_p],
     "mbk_pool_conv_fwd4": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     "mbk_res_blk32_fwd_wave": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
@@ -167,7 +172,7 @@ _SIGS = {
     "mbk_res_bwd32_team": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                            c_int, c_int, c_int, c_int, c_void_p],
     "mbk_res_bwd16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                      c_int, c_int, c_int, c_int, c_void_p],
+                      c_int, c_int, c_int, c_void_p],
     # gridnet.hip
     "mbk_bits_pad": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "mbk_colsum_parts": [c_int64],

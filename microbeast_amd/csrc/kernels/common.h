@@ -6,6 +6,13 @@
 
 #define MBK_WAVE 64
 
+// bf16 storage and the MFMA operand / accumulator vectors
+typedef __hip_bfloat16 bf16;
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef short s16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
 // Learner persistent grids: resident workgroups per CU capped at mbk_occ_cap(0) (forward
 // kernels) / mbk_occ_cap(1) (backward kernels), 0 = no cap. The acting kernels (215-256
 // VGPRs) cannot co-reside with two learner workgroups per CU (2 waves x ~224 VGPRs per SIMD)
@@ -231,6 +238,41 @@ __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+// compiler-only ordering point between a wave's LDS writes and its later reads of them (the
+// hardware completes one wave's LDS instructions in order)
+__device__ __forceinline__ void wave_lds_order() { asm volatile("" ::: "memory"); }
+
+// ------------------------------------------------------------------ bf16 values and pairs
+__device__ __forceinline__ float bf2f(bf16 v) { return __bfloat162float(v); }
+__device__ __forceinline__ bf16 f2bf(float v) { return __float2bfloat16(v); }
+// the halves of a packed bf16 pair as floats, and a pair from two floats
+__device__ __forceinline__ float lo_f(uint32_t w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float hi_f(uint32_t w) { return __uint_as_float(w & 0xFFFF0000u); }
+__device__ __forceinline__ uint32_t pack2(float a, float b) {
+  return (uint32_t)__bfloat16_as_ushort(__float2bfloat16(a)) |
+         ((uint32_t)__bfloat16_as_ushort(__float2bfloat16(b)) << 16);
+}
+__device__ __forceinline__ uint32_t cvt_pk2(float a, float b) {  // v_cvt_pk_bf16_f32 (RNE)
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  typedef __bf16 b16x2 __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, b16x2));
+}
+// relu of a bf16 pair in ONE v_pk_max_i16: a bf16 with the sign bit set is a negative
+// int16 (-0.0 = 0x8000 too), a non-negative one a non-negative int16, so the signed max
+// with 0 is exactly relu (the bit-select form costs ~6 VALU per dword, and the trunk
+// re-applies relu for all 9 taps of every input pixel: profile 15, VALU-bound)
+__device__ __forceinline__ uint32_t relu2(uint32_t w) {
+  s16x2 v = __builtin_bit_cast(s16x2, w);
+  v = __builtin_elementwise_max(v, s16x2{0, 0});
+  return __builtin_bit_cast(uint32_t, v);
+}
+
+// ds_read_b64_tr_b16: the transposed LDS read of the weight-gradient GEMMs' operands
+__device__ __forceinline__ s16x4 tr_read(const char* lds_addr) {
+  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (s16x4 __attribute__((address_space(3)))*)(uintptr_t)(lds_addr));
 }
 
 // ------------------------------------------------------------------ critic order

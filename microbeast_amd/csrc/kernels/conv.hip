@@ -36,26 +36,9 @@
 
 using namespace mbk;
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __hip_bfloat16 bf16;
-
 namespace {
 
 constexpr int kThreads = 256;
-
-__device__ __forceinline__ float bf2f(bf16 v) { return __bfloat162float(v); }
-__device__ __forceinline__ bf16 f2bf(float v) { return __float2bfloat16(v); }
-
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t relu_bf16x2(uint32_t w) {
-  // bf16 pair: sign bit set (negative, -0) -> +0 as ONE v_pk_max_i16 (a bf16 with the
-  // sign bit set is a negative int16, a non-negative one a non-negative int16)
-  s16x2 v = __builtin_bit_cast(s16x2, w);
-  v = __builtin_elementwise_max(v, s16x2{0, 0});
-  return __builtin_bit_cast(uint32_t, v);
-}
 
 union Frag8 {
   bf16x8 v;
@@ -218,8 +201,8 @@ __global__ __launch_bounds__(kThreads) void conv_fwd_kernel(ConvFwdArgs a) {
   };
   auto put = [&](int off, uint4 v) {
     if (a.relu_in) {
-      v.x = relu_bf16x2(v.x); v.y = relu_bf16x2(v.y);
-      v.z = relu_bf16x2(v.z); v.w = relu_bf16x2(v.w);
+      v.x = relu2(v.x); v.y = relu2(v.y);
+      v.z = relu2(v.z); v.w = relu2(v.w);
     }
     if constexpr (F8) *(uint2*)(tile + off) = bf16x8_to_fp8(v);
     else *(uint4*)(tile + off) = v;
@@ -740,11 +723,6 @@ struct ConvWgradArgs {
   int* queue = nullptr;
 };
 
-__device__ __forceinline__ s16x4 tr_read(const char* lds_addr) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (s16x4 __attribute__((address_space(3)))*)(uintptr_t)(lds_addr));
-}
-
 constexpr int kPFW = 4;  // wgrad prefetch slots per thread for X and for dY
 #ifndef MBK_WGRAD_TSH
 #define MBK_WGRAD_TSH 1  // build knob (tools/variant.py): 0 = the tap shift on X (A/B only)
@@ -903,8 +881,8 @@ __global__ __launch_bounds__(kThreads) void conv_wgrad_kernel(ConvWgradArgs a) {
   };
   auto put_x = [&](int off, uint4 v) {
     if (a.relu_in) {
-      v.x = relu_bf16x2(v.x); v.y = relu_bf16x2(v.y);
-      v.z = relu_bf16x2(v.z); v.w = relu_bf16x2(v.w);
+      v.x = relu2(v.x); v.y = relu2(v.y);
+      v.z = relu2(v.z); v.w = relu2(v.w);
     }
     *(uint4*)(xt + off) = v;
   };
@@ -1730,6 +1708,36 @@ inline size_t fwd_smem(int cin, int imgs, int H, int W, int cout, bool pool, boo
   return t;
 }
 
+// Images per forward / dgrad workgroup iteration: about kFwdPix output pixels, at most kFwdLds
+// of LDS (3 workgroups per CU), and one group's interior inside the register prefetch
+// (0: no such layer)
+constexpr int kFwdPix = 512;
+constexpr size_t kFwdLds = 48 * 1024;
+int fwd_imgs(int cin, int cout, int H, int W, bool bits, bool pool, bool fp8) {
+  if (cin < 8 || H < 1 || W < 1) return 0;
+  const int hw = H * W, epp = bits ? 1 : cin / 8;
+  int imgs = std::max(1, kFwdPix / hw);
+  while (imgs > 1 && (fwd_smem(cin, imgs, H, W, cout, pool, fp8) > kFwdLds ||
+                      imgs * hw * epp > kPF * kThreads))
+    imgs /= 2;
+  return imgs;
+}
+
+// Images per weight-gradient round: both operands of a round inside the register prefetch and
+// the two tiles (without their 2 x 64 pad bytes) inside 64 KB, so two workgroups fit a CU.
+// cin > cout: the halo'd dY tile is ~4 % larger and gets 72 KB, which keeps the stage-0 form's
+// 2 images per round with two workgroups per CU still fitting. unpool_imgs > 0 (the pool-fused
+// stage-0 form, which scatters one image per 32-lane half): at most that many. (0: no such layer)
+int wgrad_imgs(int cin, int cout, int H, int W, bool bits, int unpool_imgs) {
+  if (cin < 8 || cout < 8 || H < 1 || W < 1) return 0;
+  const int hw = H * W, xepp = bits ? 1 : cin / 8, pf = kPFW * kThreads;
+  int imgs = std::max(1, std::min(pf / (hw * xepp), pf / (hw * (cout / 8))));
+  if (unpool_imgs > 0) imgs = std::min(imgs, unpool_imgs);
+  const size_t lim = (cin > cout ? 72 : 64) * 1024;
+  while (imgs > 1 && wg_tile_bytes(cin, cout, imgs, H, W, wg_band_w(H, W)) - 128 > lim) imgs /= 2;
+  return imgs;
+}
+
 // (the same for the pool-fused form: it keeps its pooled operands in registers)
 inline size_t wgrad_smem(int cin, int cout, int imgs, int H, int W) {
   size_t t = wg_tile_bytes(cin, cout, imgs, H, W, wg_band_w(H, W));
@@ -1771,10 +1779,10 @@ bool index_math_ok(int imgs, int H, int W) {
 static int conv_fwd_launch(const void* x, int in_bits, int cin, int cout, const void* w,
                            const float* wscale, const float* bias, const void* add,
                            const void* mask_src, void* y, void* y_full, void* pool_idx, int N,
-                           int H, int W, int imgs, int relu_in, int pool, bool fp8,
-                           hipStream_t stream) {
+                           int H, int W, int relu_in, int pool, bool fp8, hipStream_t stream) {
   if (N <= 0) return 0;
   if (fp8 && !wscale) return (int)hipErrorInvalidValue;
+  const int imgs = fwd_imgs(cin, cout, H, W, in_bits != 0, pool != 0, fp8);
   if (!index_math_ok(imgs, H, W)) return (int)hipErrorInvalidValue;
   ConvFwdArgs a{x, (const bf16*)w, bias, (const bf16*)add, (const bf16*)mask_src, (bf16*)y,
                 (bf16*)y_full, (uint8_t*)pool_idx, N, H, W, imgs, relu_in, pool, wscale};
@@ -1826,20 +1834,25 @@ static int conv_fwd_launch(const void* x, int in_bits, int cin, int cout, const 
 
 extern "C" int mbk_conv_fwd(const void* x, int in_bits, int cin, int cout, const void* w,
                             const float* bias, const void* add, const void* mask_src, void* y,
-                            void* y_full, void* pool_idx, int N, int H, int W, int imgs,
-                            int relu_in, int pool, hipStream_t stream) {
+                            void* y_full, void* pool_idx, int N, int H, int W, int relu_in,
+                            int pool, hipStream_t stream) {
   return conv_fwd_launch(x, in_bits, cin, cout, w, nullptr, bias, add, mask_src, y, y_full,
-                         pool_idx, N, H, W, imgs, relu_in, pool, false, stream);
+                         pool_idx, N, H, W, relu_in, pool, false, stream);
 }
 
 // Inference conv on fp8 MFMA: w = e4m3 packed weights (mbk_conv_pack_fp8), wscale = their
 // per-output-channel dequant scale; activations in / out stay bf16 NHWC.
 extern "C" int mbk_conv_fwd_fp8(const void* x, int in_bits, int cin, int cout, const void* w,
                                 const float* wscale, const float* bias, const void* add, void* y,
-                                int N, int H, int W, int imgs, int relu_in, int pool,
-                                hipStream_t stream) {
+                                int N, int H, int W, int relu_in, int pool, hipStream_t stream) {
   return conv_fwd_launch(x, in_bits, cin, cout, w, wscale, bias, add, nullptr, y, nullptr,
-                         nullptr, N, H, W, imgs, relu_in, pool, true, stream);
+                         nullptr, N, H, W, relu_in, pool, true, stream);
+}
+
+// images per workgroup iteration of mbk_conv_fwd / mbk_conv_fwd_fp8 for this layer (a data
+// gradient is the forward of (cout, cin) without bit planes or pool); pure arithmetic
+extern "C" int mbk_conv_fwd_imgs(int in_bits, int cin, int cout, int H, int W, int pool, int fp8) {
+  return fwd_imgs(cin, cout, H, W, in_bits != 0, pool != 0, fp8 != 0);
 }
 
 // LAUNCH(CI, CO, B) for the layer's (cin, cout, bit-plane input); ERR: returned for any other
@@ -1875,30 +1888,43 @@ static int occ_b2(int per) {  // twice the backward cap
   const int c = mbk_occ_cap(1);
   return c > 0 && per > 2 * c ? 2 * c : per;
 }
-// number of partial rows mbk_conv_wgrad will write for this shape (<= nrounds)
+// images per round of mbk_conv_wgrad for this layer; pure arithmetic
+extern "C" int mbk_conv_wgrad_imgs(int in_bits, int cin, int cout, int H, int W,
+                                   int unpool_imgs) {
+  return wgrad_imgs(cin, cout, H, W, in_bits != 0, unpool_imgs);
+}
+
+// number of partial rows mbk_conv_wgrad will write for this shape (<= nrounds); unpool_imgs:
+// 0 = dY is given, 1 or 2 = the pool-fused stage-0 form with that many images per round
 extern "C" int mbk_conv_wgrad_parts(int in_bits, int cin, int cout, int N, int H, int W,
-                                    int imgs, int unpool) {
+                                    int unpool_imgs) {
+  const bool unpool = unpool_imgs > 0;
+  const int imgs = wgrad_imgs(cin, cout, H, W, in_bits != 0, unpool_imgs);
   const size_t sm = wgrad_smem(cin, cout, imgs, H, W);
   if (sm > 160 * 1024 || !index_math_ok(imgs, H, W)) return -(int)hipErrorInvalidValue;
   const int nrounds = (N + imgs - 1) / imgs;
   const void* kq = nullptr;
-#define Q(CI, CO, B) kq = wgrad_kfn<CI, CO, B>(H, W, unpool != 0)
+#define Q(CI, CO, B) kq = wgrad_kfn<CI, CO, B>(H, W, unpool)
   WGRAD_DISPATCH(Q, -(int)hipErrorInvalidValue)
 #undef Q
   if (!kq) return -(int)hipErrorInvalidValue;
   // the backward cap leaves room for one acting workgroup (80 KB of LDS) beside the learner's:
   // a pool-fused stage-0 form small enough for two of its workgroups beside it may take two
   const int res = capped_resident_blocks(
-      kq, kThreads, sm, unpool != 0 && 2 * sm + 80 * 1024 <= 160 * 1024 ? occ_b2 : mbk_occ_b);
+      kq, kThreads, sm, unpool && 2 * sm + 80 * 1024 <= 160 * 1024 ? occ_b2 : mbk_occ_b);
   return (int)std::max(1L, std::min((long)nrounds, (long)res));
 }
 
 // dy == nullptr: the stage-0 pool-fused form, dY = max_pool2d backward of dp through pidx
+// (unpool_imgs = 1 or 2, as given to mbk_conv_wgrad_parts; 0 with a dY)
 extern "C" int mbk_conv_wgrad(const void* x, int in_bits, int cin, int cout, const void* dy,
                               const void* dp, const void* pidx, float* partial, int nparts,
-                              int N, int H, int W, int imgs, int relu_in, hipStream_t stream) {
+                              int N, int H, int W, int unpool_imgs, int relu_in,
+                              hipStream_t stream) {
   const bool unpool = dy == nullptr;
-  if (unpool && (!dp || !pidx || imgs > 2)) return (int)hipErrorInvalidValue;
+  if (unpool != (unpool_imgs > 0) || (unpool && (!dp || !pidx || unpool_imgs > 2)))
+    return (int)hipErrorInvalidValue;
+  const int imgs = wgrad_imgs(cin, cout, H, W, in_bits != 0, unpool_imgs);
   ConvWgradArgs a{x, (const bf16*)dy, partial, N, H, W, imgs, relu_in, (const bf16*)dp,
                   (const uint8_t*)pidx};
 #ifndef MBK_WGRAD_QUEUE

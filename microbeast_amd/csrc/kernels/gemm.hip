@@ -17,10 +17,6 @@
 
 #include <algorithm>
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __hip_bfloat16 bf16;
-
 namespace {
 
 constexpr int kThreads = 256;

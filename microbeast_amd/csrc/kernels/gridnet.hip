@@ -15,8 +15,6 @@
 #include <algorithm>
 #include <climits>
 
-typedef __hip_bfloat16 bf16;
-
 namespace {
 
 constexpr int kThreads = 256;

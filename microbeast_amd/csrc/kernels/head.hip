@@ -42,11 +42,6 @@
 
 using namespace mbk;
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __hip_bfloat16 bf16;
-
 namespace {
 
 constexpr int KD = 256;      // feature width
@@ -58,14 +53,6 @@ union Frag8 {
   uint4 u;
   s16x4 h[2];
 };
-
-__device__ __forceinline__ float bf2f(bf16 v) { return __bfloat162float(v); }
-__device__ __forceinline__ bf16 f2bf(float v) { return __float2bfloat16(v); }
-
-__device__ __forceinline__ s16x4 tr_read(const char* lds_addr) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (s16x4 __attribute__((address_space(3)))*)(uintptr_t)(lds_addr));
-}
 
 __device__ __forceinline__ bool active3(const uint32_t* m) { return (m[0] | m[1] | m[2]) != 0u; }
 

@@ -33,10 +33,7 @@
 
 #include <algorithm>
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __hip_bfloat16 bf16;
+using namespace mbk;
 
 namespace {
 
@@ -540,11 +537,6 @@ struct PWgradArgs {
 };
 
 constexpr int WR_ = 128;  // K rows (images) per stage
-
-__device__ __forceinline__ s16x4 tr_read(const char* lds_addr) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (s16x4 __attribute__((address_space(3)))*)(uintptr_t)(lds_addr));
-}
 
 constexpr int kMaxWgPairs = 256;  // pairs per tap held in LDS
 

@@ -26,11 +26,7 @@
 #include <algorithm>
 
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __hip_bfloat16 bf16;
+using namespace mbk;
 
 namespace {
 
@@ -48,23 +44,8 @@ union Frag8 {
   s16x4 h[2];
 };
 
-__device__ __forceinline__ uint32_t relu2(uint32_t w) {
-  s16x2 v = __builtin_bit_cast(s16x2, w);
-  v = __builtin_elementwise_max(v, s16x2{0, 0});
-  return __builtin_bit_cast(uint32_t, v);
-}
 __device__ __forceinline__ uint4 relu8(uint4 v) {
   return make_uint4(relu2(v.x), relu2(v.y), relu2(v.z), relu2(v.w));
-}
-__device__ __forceinline__ float lo_f(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float hi_f(uint32_t w) { return __uint_as_float(w & 0xFFFF0000u); }
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  return (uint32_t)__bfloat16_as_ushort(__float2bfloat16(a)) |
-         ((uint32_t)__bfloat16_as_ushort(__float2bfloat16(b)) << 16);
-}
-__device__ __forceinline__ s16x4 tr_read(const char* lds_addr) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (s16x4 __attribute__((address_space(3)))*)(uintptr_t)(lds_addr));
 }
 
 // 8x8-map tile geometry of the wave-owned kernels (res_fwd16_w88 / res_bwd16_w88): lay16(8, 8)
@@ -74,16 +55,6 @@ constexpr int IMGB = ((H + 1) * RB + (W + 2) * PB + 15) & ~15;  // lay16(8, 8).i
 constexpr int REG = 3 * IMGB;  // a wave's LDS: Tx, Tr, Tu
 constexpr int TX = 0, TR = IMGB, TU = 2 * IMGB;
 }  // namespace w88
-
-__device__ __forceinline__ uint32_t cvt_pk2(float a, float b) {  // v_cvt_pk_bf16_f32 (RNE)
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef __bf16 b16x2 __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, b16x2));
-}
-
-// compiler-only ordering point between a wave's LDS writes and its later reads of them (the
-// hardware completes one wave's LDS instructions in order)
-__device__ __forceinline__ void wave_lds_order() { asm volatile("" ::: "memory"); }
 
 struct ResBwdArgs {
   const bf16* x;     // block input (pre-relu)      [N][H][W][16]
@@ -684,6 +655,22 @@ size_t res_smem(int imgs, int H, int W) {
   return 4 * tb + 64;
 }
 
+// Images per round of the fused residual kernels below: as many as fit the LDS a CU has left
+// beside an 80 KB acting workgroup. These rules count a halo'd pixel at the plain layouts' bytes
+// (PIXB / PIXB32), not at lay16 / geo32f / geo32's padded ones, on purpose: the padded 4- and
+// 8-wide layouts would give other round sizes (res_blk32 4x4: 16 for 14, res_bwd32 4x4: 10 for
+// 8, res_bwd16 12x8: 2 for 3), and a round size is part of the weight gradients' summation
+// order and of the measured speed. The launchers check the real bytes (*_smem) afterwards.
+constexpr int kLdsBesideActing = 80 * 1024;
+int plain_tile_imgs(int lds, int tiles, int H, int W, int pixb) {
+  return lds / (tiles * (H + 2) * (W + 2) * pixb);
+}
+// (0: no such map, for every rule)
+int res_bwd16_imgs(int H, int W) {  // four tiles: x, u, g, du
+  if (H < 1 || W < 1) return 0;
+  return std::max(1, std::min(8, plain_tile_imgs(kLdsBesideActing, 4, H, W, PIXB)));
+}
+
 // the wave-owned 8x8 backward runs whole images per wave: any imgs, 4 images per round
 bool res_bwd_w88(int H, int W) { return H == 8 && W == 8; }
 
@@ -701,7 +688,8 @@ int res_grid(int N, int H, int W, int imgs) {
 }  // namespace
 
 // Number of partial row PAIRS mbk_res_bwd16 writes (= its grid); <= 0: unsupported shape.
-extern "C" int mbk_res_bwd16_parts(int N, int H, int W, int imgs) {
+extern "C" int mbk_res_bwd16_parts(int N, int H, int W) {
+  const int imgs = res_bwd16_imgs(H, W);
   if (N <= 0 || imgs < 1 || H * W > 1024 || (int64_t)imgs * H * W >= (int64_t(1) << 22))
     return -1;
   if (res_smem(imgs, H, W) > 160 * 1024) return -1;
@@ -1868,12 +1856,34 @@ size_t res32b_smem(int imgs, int H, int W) {
   return std::max(4 * tb + 128, (size_t)kT32 * 16 * 4);
 }
 
+// its four tiles get 100 KB (less the 128 pad bytes), or 150 KB on maps of <= 2x2 pixels, which
+// are mostly halo; at most kRes32Pix output pixels per round (plain-layout bytes: res_bwd16_imgs)
+constexpr int kRes32Pix = 256;
+int res_bwd32_imgs(int H, int W) {
+  if (H < 1 || W < 1) return 0;
+  const int lds = (H * W > 4 ? 100 : 150) * 1024 - 128;
+  return std::max(1, std::min(kRes32Pix / (H * W), plain_tile_imgs(lds, 4, H, W, PIXB32)));
+}
+
 size_t resb32_smem(int imgs, int H, int W) {
   return 2 * (((size_t)imgs * geo32f(H, W).is + 15) & ~(size_t)15);
+}
+int res_blk32_imgs(int H, int W) {  // two tiles
+  if (H < 1 || W < 1) return 0;
+  return std::max(1, std::min(16, plain_tile_imgs(kLdsBesideActing, 2, H, W, PIXB32)));
 }
 
 size_t resf_smem(int imgs, int H, int W) {
   return 2 * (((size_t)imgs * lay16(H, W).imgb + 15) & ~(size_t)15);
+}
+// images per round of the generic 16-channel forward (the 8x8 kernel owns an image per wave)
+constexpr int kResFwd16Imgs = 4;
+// the fused stage conv's pre-pool staging [imgs*H*W][36] bf16 (12-wide maps: unpadded 32) lives
+// in the relu(u) tile: it must fit
+bool res_fwd16_stage_ok(int H, int W) {
+  if (H < 1 || W < 1) return false;
+  return (size_t)kResFwd16Imgs * H * W * (W == 12 ? 2 * C : 2 * C + 4) * 2 <=
+         resf_smem(kResFwd16Imgs, H, W) / 2;
 }
 
 // the wave-owned 8x8 forward (res_fwd16_w88_kernel): three tiles per wave
@@ -1886,10 +1896,10 @@ static int res_fwd16_launch(ResFwdArgs a, hipStream_t stream);
 // Forward of both residual blocks of a 16-channel stage (see res_fwd16_kernel).
 extern "C" int mbk_res_fwd16(const void* p, void* u0, void* y0, void* u1, void* y1,
                              const void* const* w, const float* const* b, int N, int H, int W,
-                             int imgs, hipStream_t stream) {
+                             hipStream_t stream) {
   ResFwdArgs a{(const bf16*)p, (bf16*)u0, (bf16*)y0, (bf16*)u1, (bf16*)y1,
                {(const bf16*)w[0], (const bf16*)w[1], (const bf16*)w[2], (const bf16*)w[3]},
-               {b[0], b[1], b[2], b[3]}, N, H, W, imgs, nullptr, nullptr, nullptr, nullptr};
+               {b[0], b[1], b[2], b[3]}, N, H, W, kResFwd16Imgs, nullptr, nullptr, nullptr, nullptr};
   return res_fwd16_launch(a, stream);
 }
 
@@ -1899,11 +1909,11 @@ extern "C" int mbk_res_fwd16(const void* p, void* u0, void* y0, void* u1, void* 
 extern "C" int mbk_res_fwd16_stage(const void* p, void* u0, void* y0, void* u1, void* y1,
                                    const void* const* w, const float* const* b, const void* ws,
                                    const float* bs, void* ps, void* pidx, int N, int H, int W,
-                                   int imgs, hipStream_t stream) {
+                                   hipStream_t stream) {
   if (!ws || !bs || !ps) return (int)hipErrorInvalidValue;
   ResFwdArgs a{(const bf16*)p, (bf16*)u0, (bf16*)y0, (bf16*)u1, (bf16*)y1,
                {(const bf16*)w[0], (const bf16*)w[1], (const bf16*)w[2], (const bf16*)w[3]},
-               {b[0], b[1], b[2], b[3]}, N, H, W, imgs, (const bf16*)ws, bs, (bf16*)ps,
+               {b[0], b[1], b[2], b[3]}, N, H, W, kResFwd16Imgs, (const bf16*)ws, bs, (bf16*)ps,
                (uint8_t*)pidx};
   return res_fwd16_launch(a, stream);
 }
@@ -1911,14 +1921,11 @@ extern "C" int mbk_res_fwd16_stage(const void* p, void* u0, void* y0, void* u1, 
 static int res_fwd16_launch(ResFwdArgs a, hipStream_t stream) {
   const int N = a.N, H = a.H, W = a.W, imgs = a.imgs;
   if (N <= 0) return 0;
-  if (imgs < 1 || H * W > 1024 || (int64_t)imgs * H * W >= (int64_t(1) << 22))
-    return (int)hipErrorInvalidValue;
+  if (H < 1 || W < 1 || H * W > 1024) return (int)hipErrorInvalidValue;
   const size_t sm = resf_smem(imgs, H, W);
   if (sm > 160 * 1024) return (int)hipErrorInvalidValue;
   const bool st = a.ws != nullptr;
-  // the stage conv's pre-pool staging [imgs*H*W][36] bf16 lives in Tu
-  if (st && (size_t)imgs * H * W * (W == 12 ? 2 * C : 2 * C + 4) * 2 > sm / 2)
-    return (int)hipErrorInvalidValue;
+  if (st && !res_fwd16_stage_ok(H, W)) return (int)hipErrorInvalidValue;
   const bool fast = H == 8 && W == 8;  // (imgs: the generic kernel's round size only)
   const size_t smf = fast ? resf_w88_smem() : sm;
   if (fast) a.queue = mbk_work_queue(stream, kQueueResFwd16);
@@ -1942,9 +1949,10 @@ static int res_fwd16_launch(ResFwdArgs a, hipStream_t stream) {
 // after them; the caller reduces them (mbk_wgrad_reduce_batch).
 extern "C" int mbk_res_bwd16(const void* x, const void* u, const void* g, void* dx,
                              const void* w1t, const void* w0t, float* partial, int nparts,
-                             int N, int H, int W, int imgs, hipStream_t stream) {
+                             int N, int H, int W, hipStream_t stream) {
   if (N <= 0) return 0;
-  if (nparts < 1 || nparts != mbk_res_bwd16_parts(N, H, W, imgs)) return (int)hipErrorInvalidValue;
+  if (nparts < 1 || nparts != mbk_res_bwd16_parts(N, H, W)) return (int)hipErrorInvalidValue;
+  const int imgs = res_bwd16_imgs(H, W);
   const bool fast = res_bwd_w88(H, W);
   const size_t sm = fast ? res_w88b_smem() : res_smem(imgs, H, W);
   const int64_t lstride = mbk::wgrad_partial_floats(nparts, C, C);
@@ -1960,7 +1968,8 @@ extern "C" int mbk_res_bwd16(const void* x, const void* u, const void* g, void* 
 
 // Partial-row PAIRS mbk_res_bwd32 writes (= its grid: one 8-wave workgroup per CU);
 // <= 0: unsupported shape.
-extern "C" int mbk_res_bwd32_parts(int N, int H, int W, int imgs) {
+extern "C" int mbk_res_bwd32_parts(int N, int H, int W) {
+  const int imgs = res_bwd32_imgs(H, W);
   if (N <= 0 || imgs < 1 || H * W > 1024 || (int64_t)imgs * H * W >= (int64_t(1) << 22))
     return -1;
   if (res32b_smem(imgs, H, W) > 160 * 1024) return -1;
@@ -2008,9 +2017,10 @@ extern "C" int mbk_res_bwd32_team(const void* x, const void* u, const void* g, v
 // weight / bias gradients, laid out and reduced as mbk_res_bwd16's.
 extern "C" int mbk_res_bwd32(const void* x, const void* u, const void* g, void* dx,
                              const void* w1t, const void* w0t, float* partial, int nparts,
-                             int N, int H, int W, int imgs, hipStream_t stream) {
+                             int N, int H, int W, hipStream_t stream) {
   if (N <= 0) return 0;
-  if (nparts < 1 || nparts != mbk_res_bwd32_parts(N, H, W, imgs)) return (int)hipErrorInvalidValue;
+  if (nparts < 1 || nparts != mbk_res_bwd32_parts(N, H, W)) return (int)hipErrorInvalidValue;
+  const int imgs = res_bwd32_imgs(H, W);
   const size_t sm = res32b_smem(imgs, H, W);
   const int64_t lstride = mbk::wgrad_partial_floats(nparts, C32, C32);
   ResBwd32Args a{(const bf16*)x, (const bf16*)u, (const bf16*)g, (bf16*)dx,
@@ -2055,9 +2065,10 @@ extern "C" int mbk_res_blk32_fwd_wave(const void* x, void* u, void* y, const voi
 }
 
 extern "C" int mbk_res_blk32_fwd(const void* x, void* u, void* y, const void* const* w,
-                                 const float* const* b, int N, int H, int W, int imgs,
+                                 const float* const* b, int N, int H, int W,
                                  hipStream_t stream) {
   if (N <= 0) return 0;
+  const int imgs = res_blk32_imgs(H, W);
   if (imgs < 1 || H * W > 1024 || (int64_t)imgs * H * W >= (int64_t(1) << 22))
     return (int)hipErrorInvalidValue;
   const size_t sm = resb32_smem(imgs, H, W);
@@ -2072,3 +2083,10 @@ extern "C" int mbk_res_blk32_fwd(const void* x, void* u, void* y, const void* co
   hipLaunchKernelGGL(kfn, dim3(std::max(1, std::min(nrounds, res))), dim3(kThreads), sm, stream, a);
   return (int)hipGetLastError();
 }
+
+// Images per round the launchers above choose (pure arithmetic, no device needed), and whether
+// mbk_res_fwd16_stage takes an H x W stage (1) or rejects it (0).
+extern "C" int mbk_res_bwd16_imgs(int H, int W) { return res_bwd16_imgs(H, W); }
+extern "C" int mbk_res_blk32_fwd_imgs(int H, int W) { return res_blk32_imgs(H, W); }
+extern "C" int mbk_res_bwd32_imgs(int H, int W) { return res_bwd32_imgs(H, W); }
+extern "C" int mbk_res_fwd16_stage_ok(int H, int W) { return res_fwd16_stage_ok(H, W); }

@@ -20,9 +20,7 @@
 
 #include <algorithm>
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __hip_bfloat16 bf16;
+using namespace mbk;
 
 namespace {
 
@@ -30,13 +28,6 @@ union Frag8 {
   bf16x8 v;
   uint4 u;
 };
-
-__device__ __forceinline__ uint32_t cvt_pk2(float a, float b) {
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef __bf16 b16x2 __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, b16x2));
-}
-__device__ __forceinline__ void wave_lds_order() { asm volatile("" ::: "memory"); }
 
 namespace s2 {
 constexpr int H = 4, W = 4, HW = 16, C = 32, HO = 2, WO = 2;

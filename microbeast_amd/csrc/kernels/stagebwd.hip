@@ -32,10 +32,7 @@
 
 #include <algorithm>
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __hip_bfloat16 bf16;
+using namespace mbk;
 
 namespace {
 
@@ -44,17 +41,6 @@ union Frag8 {
   uint4 u;
   s16x4 h[2];
 };
-
-__device__ __forceinline__ s16x4 tr_read(const char* lds_addr) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (s16x4 __attribute__((address_space(3)))*)(uintptr_t)(lds_addr));
-}
-__device__ __forceinline__ uint32_t cvt_pk2(float a, float b) {
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef __bf16 b16x2 __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, b16x2));
-}
-__device__ __forceinline__ void wave_lds_order() { asm volatile("" ::: "memory"); }
 
 // ---- geometry (stage 1 at 16x16): x 8x8x16, dc 8x8x32, pooled 4x4x32
 namespace s1 {

@@ -29,9 +29,7 @@
 #include <cstdlib>
 #include <string>
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __hip_bfloat16 bf16;
+using namespace mbk;
 
 namespace {
 
@@ -43,23 +41,6 @@ union Frag8 {
   bf16x8 v;
   uint4 u;
 };
-
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-// relu of a bf16 pair in ONE v_pk_max_i16: a bf16 with the sign bit set is a negative
-// int16 (-0.0 = 0x8000 too), a non-negative one a non-negative int16, so the signed max
-// with 0 is exactly relu (the bit-select form costs ~6 VALU per dword, and the trunk
-// re-applies relu for all 9 taps of every input pixel: profile 15, VALU-bound)
-__device__ __forceinline__ uint32_t relu2(uint32_t w) {
-  s16x2 v = __builtin_bit_cast(s16x2, w);
-  v = __builtin_elementwise_max(v, s16x2{0, 0});
-  return __builtin_bit_cast(uint32_t, v);
-}
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  return (uint32_t)__bfloat16_as_ushort(__float2bfloat16(a)) |
-         ((uint32_t)__bfloat16_as_ushort(__float2bfloat16(b)) << 16);
-}
-__device__ __forceinline__ float lo_f(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float hi_f(uint32_t w) { return __uint_as_float(w & 0xFFFF0000u); }
 
 template <int C>
 struct TG {

@@ -62,59 +62,6 @@ def _nch(c: int) -> int:
 PLANE_GROUPS = ((0, 5), (5, 5), (10, 3), (13, 8), (21, 6))
 EMPTY_WORD = sum(1 << off for off, _ in PLANE_GROUPS)
 
-_PF_FWD = 8 * 256    # conv_fwd register-prefetch capacity (elements per group)
-_PF_WGRAD = 4 * 256  # conv_wgrad prefetch capacity, X and dY each
-# conv_fwd workgroup sizing (tools/microbench.py sweeps): LDS budget per workgroup (48 KB =
-# 3 workgroups per CU) and the target output pixels per image group
-_FWD_LDS = 48 * 1024
-_FWD_PIX = 512
-# res_bwd32 round size: output pixels per round and the LDS budget (KB) of its four tiles
-# (maps of <= 2x2 pixels are mostly halo: their own budget)
-_RES32_PIX = 256
-_RES32_LDS_KB = 100
-_RES32_LDS_KB_SMALL = 150
-
-
-def _imgs_fwd(layer: ConvLayer, cin: int, cout: int, bits: bool, pool: bool,
-              fp8: bool = False) -> int:
-    """Images per workgroup iteration: ~512 output pixels, <= 48 KB LDS (3 WGs / CU), and
-    one group's interior fits the register prefetch."""
-    hw = layer.H * layer.W
-    epp = 1 if bits else cin // 8
-    pixb = (cin + 8) if fp8 else (cin * 2 + 16)  # bit planes are expanded in LDS
-    imgs = max(1, _FWD_PIX // hw)
-    while imgs > 1:
-        sm = imgs * (layer.H + 2) * (layer.W + 2) * pixb + (imgs * hw * (cout + 4) * 2 if pool else 0)
-        if sm <= _FWD_LDS and imgs * hw * epp <= _PF_FWD:
-            break
-        imgs //= 2
-    return imgs
-
-
-def _imgs_wgrad(layer: ConvLayer, unpool: bool = False, unpool_imgs: int = 2) -> int:
-    hw = layer.H * layer.W
-    xepp = 1 if layer.bits else layer.cin // 8
-    dch = layer.cout // 8
-    imgs = max(1, min(_PF_WGRAD // (hw * xepp), _PF_WGRAD // (hw * dch)))
-    # LDS per image: conv.hip wg_tile_bytes (band layout on 8 / 16 / 24-wide maps pads the rows)
-    if layer.W in (8, 16, 24) and layer.H % 4 == 0:
-        rbx = (layer.W + 2) * layer.cin * 2 + (32 if layer.cin == 32 else 64)
-        rbd = layer.W * layer.cout * 2 + (32 if layer.cout == 32 else 128)
-        # (cin > cout: the tap-shifted dY tile has a zero halo: H + 2 rows)
-        per = (layer.H + 2) * rbx + (layer.H + (2 if layer.cin > layer.cout else 0)) * rbd
-    else:
-        per = (layer.H + 2) * (layer.W + 2) * layer.cin * 2 + hw * layer.cout * 2
-    if unpool:  # the pool-fused form scatters 2 images per round (one per 32-lane half)
-        imgs = min(imgs, unpool_imgs)
-    # (the halo'd dY tile is ~4 % larger: the stage-0 form keeps its 2 images per round, two
-    # workgroups per CU still fit)
-    lim = (72 if layer.cin > layer.cout else 64) * 1024
-    while imgs > 1:
-        if imgs * per <= lim:
-            break
-        imgs //= 2
-    return imgs
-
 
 class HipEncoder:
     """Owns layer geometry, packed-weight buffers and backward workspace."""
@@ -247,11 +194,10 @@ class HipEncoder:
         n = x.shape[0]
         Ho, Wo = ((L.H + 1) // 2, (L.W + 1) // 2) if L.pool else (L.H, L.W)
         y = torch.empty(n, Ho, Wo, L.cout, dtype=torch.bfloat16, device=x.device)
-        imgs = _imgs_fwd(L, L.cin, L.cout, L.bits, L.pool, fp8=True)
         N.check(N.kernels().mbk_conv_fwd_fp8(
             x.data_ptr(), int(L.bits), L.cin, L.cout, self.packed_fwd8.data_ptr() + L.w_off,
             self.scale8.data_ptr() + 4 * self._s_off[i], N.ptr(bias), N.ptr(add), y.data_ptr(),
-            n, L.H, L.W, imgs, int(L.relu_in), int(L.pool), N.stream_ptr()), "conv_fwd_fp8")
+            n, L.H, L.W, int(L.relu_in), int(L.pool), N.stream_ptr()), "conv_fwd_fp8")
         return y
 
     def _tail(self, p: torch.Tensor, bs: list[torch.Tensor], head=None, value_out=None):
@@ -310,10 +256,9 @@ class HipEncoder:
             H, W, bits, relu, pool = L.H, L.W, L.bits, L.relu_in, L.pool
         Ho, Wo = ((H + 1) // 2, (W + 1) // 2) if pool else (H, W)
         y = torch.empty(n, Ho, Wo, cout, dtype=torch.bfloat16, device=x.device)
-        imgs = _imgs_fwd(L, cin, cout, bits, pool)
         N.check(N.kernels().mbk_conv_fwd(
             x.data_ptr(), int(bits), cin, cout, w, N.ptr(bias), N.ptr(add), N.ptr(mask_src),
-            y.data_ptr(), N.ptr(y_full), N.ptr(pool_idx), n, H, W, imgs, int(relu), int(pool),
+            y.data_ptr(), N.ptr(y_full), N.ptr(pool_idx), n, H, W, int(relu), int(pool),
             N.stream_ptr()), "conv_fwd")
         return y
 
@@ -322,10 +267,10 @@ class HipEncoder:
         """dy=None: dY is max_pool2d's backward of dp through the argmax bytes pidx, expanded
         in the kernel's staging (the stage-0 layer of a 16-wide map)."""
         n = x.shape[0]
-        imgs = _imgs_wgrad(L, unpool=dy is None, unpool_imgs=self.wgrad0_imgs)
+        unpool_imgs = self.wgrad0_imgs if dy is None else 0
         # persistent grid: as many workgroups as the device keeps resident (<= rounds)
-        nparts = N.kernels().mbk_conv_wgrad_parts(int(L.bits), L.cin, L.cout, n, L.H, L.W, imgs,
-                                                  int(dy is None))
+        nparts = N.kernels().mbk_conv_wgrad_parts(int(L.bits), L.cin, L.cout, n, L.H, L.W,
+                                                  unpool_imgs)
         if nparts < 1:
             raise RuntimeError(f"conv_wgrad: unsupported shape {L}")
         part, _ = self._part_rows(L, nparts, 1, x.device)
@@ -333,7 +278,7 @@ class HipEncoder:
         st = N.stream_ptr()
         N.check(k.mbk_conv_wgrad(x.data_ptr(), int(L.bits), L.cin, L.cout, N.ptr(dy),
                                  N.ptr(dp), N.ptr(pidx), part.data_ptr(), nparts, n,
-                                 L.H, L.W, imgs, int(L.relu_in), st), "conv_wgrad")
+                                 L.H, L.W, unpool_imgs, int(L.relu_in), st), "conv_wgrad")
         self._reduce(part.data_ptr(), nparts, L, dw, db)
 
     def _wgrad0_sparse(self, L: ConvLayer, x, dp, pidx, dw: torch.Tensor, db: torch.Tensor):
@@ -398,7 +343,7 @@ class HipEncoder:
         if stage is None:
             N.check(k.mbk_res_fwd16(p.data_ptr(), *[o.data_ptr() for o in outs],
                                     ctypes.cast(wp, ctypes.c_void_p),
-                                    ctypes.cast(bp, ctypes.c_void_p), n, H, W, 4,
+                                    ctypes.cast(bp, ctypes.c_void_p), n, H, W,
                                     N.stream_ptr()), "res_fwd16")
             return outs
         Ln = self.layers[li + 5]
@@ -410,7 +355,7 @@ class HipEncoder:
                                       ctypes.cast(wp, ctypes.c_void_p),
                                       ctypes.cast(bp, ctypes.c_void_p),
                                       base + 2 * Ln.w_off, bs[li + 5].data_ptr(),
-                                      pn.data_ptr(), N.ptr(pidx), n, H, W, 4,
+                                      pn.data_ptr(), N.ptr(pidx), n, H, W,
                                       N.stream_ptr()), "res_fwd16_stage")
         return (*outs, (pn, pidx))
 
@@ -438,10 +383,9 @@ class HipEncoder:
                                                        ctypes.cast(bp, ctypes.c_void_p), n, H, W,
                                                        N.stream_ptr()), "res_blk32_fwd_wave")
             return u, y
-        imgs = max(1, min(16, (80 * 1024) // (2 * (H + 2) * (W + 2) * 80)))
         N.check(N.kernels().mbk_res_blk32_fwd(x.data_ptr(), u.data_ptr(), y.data_ptr(),
                                               ctypes.cast(wp, ctypes.c_void_p),
-                                              ctypes.cast(bp, ctypes.c_void_p), n, H, W, imgs,
+                                              ctypes.cast(bp, ctypes.c_void_p), n, H, W,
                                               N.stream_ptr()), "res_blk32_fwd")
         return u, y
 
@@ -451,16 +395,15 @@ class HipEncoder:
         n = x.shape[0]
         H, W = L0.H, L0.W
         k = N.kernels()
-        imgs = max(1, min(8, (80 * 1024) // (4 * (H + 2) * (W + 2) * 48)))
         dx = torch.empty_like(x)
         base = self.packed_bwd.data_ptr()
-        nparts = k.mbk_res_bwd16_parts(n, H, W, imgs)
+        nparts = k.mbk_res_bwd16_parts(n, H, W)
         if nparts < 1:
             raise RuntimeError(f"res_bwd16: unsupported shape {H}x{W}")
         part, stride = self._part_rows(L0, nparts, 2, x.device)
         N.check(k.mbk_res_bwd16(x.data_ptr(), u.data_ptr(), g.data_ptr(), dx.data_ptr(),
                                 base + 2 * L1.wb_off, base + 2 * L0.wb_off, part.data_ptr(),
-                                nparts, n, H, W, imgs, N.stream_ptr()), "res_bwd16")
+                                nparts, n, H, W, N.stream_ptr()), "res_bwd16")
         self._reduce(part.data_ptr(), nparts, L1, dw1, db1)
         self._reduce(part.data_ptr() + 4 * stride, nparts, L0, dw0, db0)
         return dx
@@ -488,20 +431,18 @@ class HipEncoder:
         k = N.kernels()
         if self.fused_res_bwd32_team and H == W and W in (2, 4):
             # wave teams on 32-pixel items, no workgroup barriers (resblock.hip)
-            name, fn, tail = "res_bwd32_team", k.mbk_res_bwd32_team, ()
+            name, fn = "res_bwd32_team", k.mbk_res_bwd32_team
             nparts = k.mbk_res_bwd32_team_parts(n, H, W)
         else:
-            lds_kb = _RES32_LDS_KB if H * W > 4 else _RES32_LDS_KB_SMALL
-            imgs = max(1, min(_RES32_PIX // (H * W), (lds_kb * 1024 - 128) // (4 * (H + 2) * (W + 2) * 80)))
-            name, fn, tail = "res_bwd32", k.mbk_res_bwd32, (imgs,)
-            nparts = k.mbk_res_bwd32_parts(n, H, W, imgs)
+            name, fn = "res_bwd32", k.mbk_res_bwd32
+            nparts = k.mbk_res_bwd32_parts(n, H, W)
             if nparts < 1:
                 raise RuntimeError(f"res_bwd32: unsupported shape {H}x{W}")
         dx = torch.empty_like(x)
         base = self.packed_bwd.data_ptr()
         part, stride = self._part_rows(L0, nparts, 2, x.device)
         N.check(fn(x.data_ptr(), u.data_ptr(), g.data_ptr(), dx.data_ptr(), base + 2 * L1.wb_off,
-                   base + 2 * L0.wb_off, part.data_ptr(), nparts, n, H, W, *tail, N.stream_ptr()),
+                   base + 2 * L0.wb_off, part.data_ptr(), nparts, n, H, W, N.stream_ptr()),
                 name)
         self._reduce(part.data_ptr(), nparts, L1, dw1, db1)
         self._reduce(part.data_ptr() + 4 * stride, nparts, L0, dw0, db0)
@@ -555,10 +496,8 @@ class HipEncoder:
                 Ln = self.layers[li + 5] if li + 5 < len(self.layers) else None
                 if (self.fused_stage_fwd and Ln is not None and Ln.cin == 16 and Ln.cout == 32
                         and Ln.pool and not Ln.bits
-                        # its pre-pool staging aliases the relu(u) tile (8x8, 5x5: fits;
-                        # 12x12 with unpadded 64-byte staging rows)
-                        and Ln.H * Ln.W * (64 if Ln.W == 12 else 72)
-                        <= (Ln.H + 2) * (Ln.W + 2) * 48):
+                        # (its pre-pool staging aliases the relu(u) tile: it must fit)
+                        and N.kernels().mbk_res_fwd16_stage_ok(Ln.H, Ln.W)):
                     u0, y0, u1, y1, nxt = self._res_fwd16(li, p, [b.detach() for b in bs],
                                                           stage=save)
                 else:
@@ -622,7 +561,7 @@ class HipEncoder:
             if (s == 0 and Ls.bits and Ls.W == 16 and self.fused_pool_wgrad0 and x.is_cuda
                     and N.kernels().mbk_conv_wgrad_parts(
                         int(Ls.bits), Ls.cin, Ls.cout, x.shape[0], Ls.H, Ls.W,
-                        _imgs_wgrad(Ls, True, self.wgrad0_imgs), 1) > 0):
+                        self.wgrad0_imgs) > 0):
                 if self.sparse_wgrad0 and (Ls.H, Ls.cin, Ls.cout) == (16, 32, 16):
                     self._wgrad0_sparse(Ls, x, dp, pidx, grads[2 * li], grads[2 * li + 1])
                 else:
