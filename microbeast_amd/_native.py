@@ -73,6 +73,11 @@ _SIGS = {
     "mbk_ppo_loss": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                      c_void_p, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float,
                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "mbk_adv_stats_rows": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "mbk_ppo_loss_rows": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                          c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_float,
+                          c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                          c_void_p, c_void_p],
     "mbk_grad_clip_scale": [c_void_p, c_int64, c_float, c_float, c_void_p, c_void_p, c_void_p],
     "mbk_adam": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float,
                  c_float, c_float, c_float, c_int64, c_void_p, c_float, c_void_p],

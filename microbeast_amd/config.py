@@ -57,8 +57,13 @@ class Flags:
     gae_lambda: float = 0.95      # ppo: GAE lambda
     ppo_clip: float = 0.1         # ppo: ratio clip eps
     ppo_value_clip: float = 0.1   # ppo: value clip eps_v (0 = unclipped value loss)
-    ppo_epochs: int = 1           # ppo: full-batch optimiser steps per rollout
+    ppo_epochs: int = 1           # ppo: passes over the rollout (epochs)
     ppo_norm_adv: bool = True     # ppo: normalise advantages over the rank's batch
+    ppo_minibatches: int = 1      # ppo: K optimiser steps per epoch, each on one block of
+                                  # unroll_length / K consecutive rows of the rollout, all envs
+    ppo_shuffle: bool = True      # ppo: visit the K blocks in a fresh random order each epoch
+    ppo_target_kl: float = 0.0    # ppo: > 0: no further optimiser step on a rollout once a
+                                  # step's approx_kl exceeds it (that step is applied); 0 = off
     # --- environment
     env: str = "synthetic"        # synthetic | microrts (gym-microrts adapter, if installed)
     opponents: str = "coac,coac,coac,random_biased,light_rush,worker_rush"

@@ -128,6 +128,23 @@ int mbk_ppo_loss(const float* logp_new, const float* logp_old, const float* valu
                  const float* stats, int T, int B, float clip_lo, float clip_hi, float clip,
                  float value_clip, float baseline_cost, float entropy_cost, float* g_logp,
                  float* g_value, float* partials, float* losses, hipStream_t stream);
+// Row-block minibatches: block k = rows [k T/K, (k+1) T/K) of the rollout, all B columns.
+// stats[K][2] = each block's own (mean, 1 / (std + 1e-8)) of adv, (0, 1) when norm_adv == 0;
+// T % K == 0. partials: 3 * K * min(256, ceil(T/K * B / 256)) floats. Ordered, no atomics.
+int mbk_adv_stats_rows(const float* adv, int T, int B, int K, int norm_adv, float* partials,
+                       float* stats, hipStream_t stream);
+// mbk_ppo_loss on one block: logp_new, values, entropy, g_logp, g_value are the step's own
+// [Tm, B] arrays (no bootstrap row); logp_old, v_old, adv, ret are the rollout-wide arrays, read
+// from row t0; stats is the block's pair; M = Tm * B. losses[7] is the step's; epoch_mean[7] is
+// the running mean over the epoch's steps (step = the step's index in its epoch; 0 restarts
+// it). partials: 6 * ceil(Tm * B / 256) floats.
+int mbk_ppo_loss_rows(const float* logp_new, const float* logp_old, const float* values,
+                      const float* v_old, const float* adv, const float* ret,
+                      const float* entropy, const float* stats, int t0, int Tm, int B,
+                      float clip_lo, float clip_hi, float clip, float value_clip,
+                      float baseline_cost, float entropy_cost, int step, float* g_logp,
+                      float* g_value, float* partials, float* losses, float* epoch_mean,
+                      hipStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,13 @@
 //     losses   = pg, value, entropy, total, mean ratio, approx_kl = mean((ratio-1) - log ratio),
 //                clip_frac = mean(|ratio-1| > eps)
 //
+// Row-block minibatches (K optimiser steps per epoch, step = Tm = T/K consecutive rows, all B):
+//   mbk_adv_stats_rows  adv [T,B] -> stats [K][2]: each block's own (mean, 1 / (std + 1e-8))
+//   mbk_ppo_loss_rows   the same element pass on the step's own [Tm,B] arrays (logp_new, values,
+//     entropy, g_logp, g_value: no bootstrap row) and rows t0.. of the rollout-wide logp_old,
+//     v_old, adv, ret; M = Tm*B. Its finalize also keeps the ordered running mean of the
+//     epoch's per-step losses (epoch_mean[7]).
+//
 // Every reduction is two-pass and ordered (per-block partials, one finalize wave): no float
 // atomics, bit-reproducible between runs. The advantage statistics merge per-block
 // (n, mean, M2) triples (Chan et al.), not a global sum of squares.
@@ -239,9 +246,133 @@ __global__ __launch_bounds__(64) void ppo_finalize_kernel(const float* __restric
   }
 }
 
+// ---- row-block minibatches: per-block advantage statistics and the block loss's finalize ----
+
+// Block k = rows [k Tm, (k+1) Tm) of adv: n = Tm*B contiguous elements. gridDim = (nb, K);
+// thread j of the nb*256 of a block takes elements j, j + nb*256, ... (a fixed assignment, so
+// the moments do not depend on the run). partials [K][nb][3].
+__global__ __launch_bounds__(256) void adv_stats_rows_kernel(const float* __restrict__ adv,
+                                                             size_t n,
+                                                             float* __restrict__ partials) {
+  const float* a = adv + (size_t)blockIdx.y * n;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  Moments mo = {0.f, 0.f, 0.f};
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const float x = a[i];
+    mo.n += 1.f;
+    const float d = x - mo.mean;
+    mo.mean += d / mo.n;
+    mo.m2 += d * (x - mo.mean);
+  }
+  __shared__ Moments red[4];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  mo = wave_merge(mo);
+  if (lane == 0) red[wave] = mo;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    Moments s = red[0];
+    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) s = merge(s, red[w]);
+    float* out = partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 3;
+    out[0] = s.n;
+    out[1] = s.mean;
+    out[2] = s.m2;
+  }
+}
+
+// one wave per block k: stats[k] = mean, 1 / (std + 1e-8); (0, 1) with normalisation off
+__global__ __launch_bounds__(64) void adv_stats_rows_finalize_kernel(
+    const float* __restrict__ partials, int nb, int norm, float* __restrict__ stats) {
+  const int lane = threadIdx.x;
+  const float* p = partials + (size_t)blockIdx.x * nb * 3;
+  Moments s = {0.f, 0.f, 0.f};
+  for (int i = lane; i < nb; i += 64) s = merge(s, Moments{p[i * 3], p[i * 3 + 1], p[i * 3 + 2]});
+  s = wave_merge(s);
+  if (lane == 0) {
+    const float sd = sqrtf(fmaxf(s.m2, 0.f) / fmaxf(s.n, 1.f));
+    stats[blockIdx.x * 2 + 0] = norm ? s.mean : 0.f;
+    stats[blockIdx.x * 2 + 1] = norm ? 1.f / (sd + 1e-8f) : 1.f;
+  }
+}
+
+// ppo_finalize_kernel for one step of an epoch: losses[7] of the step, and the ordered running
+// mean of the epoch's steps so far (step 0 restarts it)
+__global__ __launch_bounds__(64) void ppo_rows_finalize_kernel(
+    const float* __restrict__ partials, int nblocks, size_t M, float baseline_cost,
+    float entropy_cost, int step, float* __restrict__ losses, float* __restrict__ epoch_mean) {
+  const int lane = threadIdx.x;
+  float s[kSums] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int i = lane; i < nblocks; i += 64)
+    for (int k = 0; k < kSums; ++k) s[k] += partials[(size_t)i * kSums + k];
+  for (int k = 0; k < kSums; ++k) s[k] = wave_sum(s[k]);
+  if (lane == 0) {
+    const float invM = 1.f / (float)M;
+    const float pg = -s[0] * invM, vl = baseline_cost * s[1] * invM, ent = s[2] * invM;
+    const float l[7] = {pg, vl, ent, pg + vl - entropy_cost * ent, s[3] * invM, s[4] * invM,
+                        s[5] * invM};
+    const float inv = 1.f / (float)(step + 1);
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+      losses[k] = l[k];
+      epoch_mean[k] = step == 0 ? l[k] : epoch_mean[k] + (l[k] - epoch_mean[k]) * inv;
+    }
+  }
+}
+
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
+// blocks of 256 lanes per row block in adv_stats_rows_kernel
+inline int stats_rows_blocks(size_t n) {
+  const size_t nb = (n + 255) / 256;
+  return (int)(nb < 256 ? nb : 256);
+}
+
 }  // namespace
+
+// partials: 3 * K * min(256, ceil(T / K * B / 256)) floats; stats [K][2]
+extern "C" int mbk_adv_stats_rows(const float* adv, int T, int B, int K, int norm_adv,
+                                  float* partials, float* stats, hipStream_t stream) {
+  if (T < 1 || B < 1 || K < 1 || K > 65535 || T % K != 0) return (int)hipErrorInvalidValue;
+  const size_t n = (size_t)(T / K) * B;
+  const int nb = stats_rows_blocks(n);
+  hipLaunchKernelGGL(adv_stats_rows_kernel, dim3(nb, K), dim3(256), 0, stream, adv, n, partials);
+  hipLaunchKernelGGL(adv_stats_rows_finalize_kernel, dim3(K), dim3(64), 0, stream, partials, nb,
+                     norm_adv, stats);
+  return (int)hipGetLastError();
+}
+
+// partials: 6 * ceil(Tm * B / 256) floats
+extern "C" int mbk_ppo_loss_rows(const float* logp_new, const float* logp_old,
+                                 const float* values, const float* v_old, const float* adv,
+                                 const float* ret, const float* entropy, const float* stats,
+                                 int t0, int Tm, int B, float clip_lo, float clip_hi, float clip,
+                                 float value_clip, float baseline_cost, float entropy_cost,
+                                 int step, float* g_logp, float* g_value, float* partials,
+                                 float* losses, float* epoch_mean, hipStream_t stream) {
+  if (t0 < 0 || Tm < 1 || B < 1 || step < 0) return (int)hipErrorInvalidValue;
+  const size_t M = (size_t)Tm * B, off = (size_t)t0 * B;
+  logp_old += off;
+  v_old += off;
+  adv += off;
+  ret += off;
+  const bool vec = B % 4 == 0 && aligned16(logp_new) && aligned16(logp_old) &&
+                   aligned16(values) && aligned16(v_old) && aligned16(adv) && aligned16(ret) &&
+                   (!entropy || aligned16(entropy)) && aligned16(g_logp) && aligned16(g_value);
+  const size_t items = vec ? M / 4 : M;
+  const size_t nb = (items + 255) / 256;
+  if (nb > 0x7fffffffull) return (int)hipErrorInvalidValue;
+  // (MB = M: the step's arrays have no bootstrap row to zero)
+  if (vec)
+    hipLaunchKernelGGL(ppo_loss_kernel<4>, dim3((unsigned)nb), dim3(256), 0, stream, logp_new,
+                       logp_old, values, v_old, adv, ret, entropy, stats, M, M, clip_lo, clip_hi,
+                       clip, value_clip, baseline_cost, g_logp, g_value, partials);
+  else
+    hipLaunchKernelGGL(ppo_loss_kernel<1>, dim3((unsigned)nb), dim3(256), 0, stream, logp_new,
+                       logp_old, values, v_old, adv, ret, entropy, stats, M, M, clip_lo, clip_hi,
+                       clip, value_clip, baseline_cost, g_logp, g_value, partials);
+  hipLaunchKernelGGL(ppo_rows_finalize_kernel, dim3(1), dim3(64), 0, stream, partials, (int)nb, M,
+                     baseline_cost, entropy_cost, step, losses, epoch_mean);
+  return (int)hipGetLastError();
+}
 
 extern "C" int mbk_gae(const float* v_old, const float* reward, const uint8_t* done, int T, int B,
                        float gamma, float lambda, float reward_clip, int norm_adv, float* adv,

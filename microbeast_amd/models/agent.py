@@ -376,6 +376,17 @@ class Agent(nn.Module):
         logp, ent = cell_head.score(logits, mask_bits, action)
         return logp, ent, value
 
+    @torch.no_grad()
+    def values(self, obs: torch.Tensor) -> torch.Tensor:
+        """fp32 values [N] only: trunk -> network.5 -> critic. No head runs and nothing is kept
+        for a backward pass (device observations: the HIP inference kernels). The PPO learner's
+        value pass over a whole slot (``Learner._learn_ppo_steps``)."""
+        f = self.features(obs)
+        if self._use_hip(obs):
+            return linear(f, self.critic).float().view(-1)
+        with self._autocast(f):
+            return self.critic(f).float().view(-1)
+
     def get_action(self, input_dict: dict, learning: bool = False, inds=(), agent_state=()):
         """Reference-compatible API (model.py:165-216) on reference-layout inputs.
 

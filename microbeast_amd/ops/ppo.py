@@ -38,10 +38,18 @@ same on both runtimes.
     losses   = [pg, value, entropy, total = pg + value - entropy_cost entropy, mean ratio,
                 approx_kl = mean((ratio-1) - log ratio), clip_frac = mean(|ratio-1| > eps)]
 
+Row-block minibatches (``--ppo_minibatches K``): block k is rows [k T/K, (k+1) T/K) of the
+rollout, all B columns -- contiguous in a time-major slot. ``adv_stats_rows`` gives every block
+its own ``stats`` pair in one launch, and ``ppo_loss_rows`` is ``ppo_loss`` on one block: the
+step's own [T/K, B] logp_new / values / entropy (no bootstrap row, so g_value is [T/K, B]) with
+rows t0.. of the rollout-wide logp_old / v_old / adv / ret and ``M = T/K * B``. It also keeps
+``epoch_mean``, the ordered running mean of the epoch's per-step losses.
+
 Device tensors run the HIP kernels (``ppo.hip``: a one-lane-per-column reverse scan with
 per-block (n, mean, M2) partials, and one vectorised elementwise pass); a missing kernel is an
-error. CPU tensors run the same maths in fp32 torch ops (``gae_torch`` / ``ppo_loss_torch``:
-the test oracle, and what the mono runtime's CPU learner runs).
+error. CPU tensors run the same maths in fp32 torch ops (``gae_torch`` / ``ppo_loss_torch`` /
+``adv_stats_rows_torch`` / ``ppo_loss_rows_torch``: the test oracle, and what the mono
+runtime's CPU learner runs).
 """
 from __future__ import annotations
 
@@ -68,6 +76,7 @@ class PPOOut:
     losses: torch.Tensor   # [7] pg, value, entropy, total, mean ratio, approx_kl, clip_frac
     adv: torch.Tensor | None = None
     ret: torch.Tensor | None = None
+    epoch_mean: torch.Tensor | None = None  # [7] block form: mean of the epoch's steps so far
 
 
 def _f(x):
@@ -135,6 +144,33 @@ def ppo_loss_torch(logp_new, logp_old, values, v_old, adv, ret, stats, entropy=N
     return PPOOut(g_logp, g_value, -entropy_cost / M, losses, adv, ret)
 
 
+def adv_stats_rows_torch(adv, K: int, norm_adv=True) -> torch.Tensor:
+    """[K, 2]: (mean, 1 / (std + 1e-8)) of each block of T / K rows of adv [T, B] (population
+    std); every pair (0, 1) with ``norm_adv`` off."""
+    T = adv.shape[0]
+    if K < 1 or T % K != 0:
+        raise ValueError(f"ppo_minibatches {K} does not divide the {T} rows of the rollout")
+    a = _f(adv).reshape(K, -1)
+    if not norm_adv:
+        return torch.tensor([[0.0, 1.0]] * K, dtype=a.dtype, device=a.device)
+    return torch.stack([a.mean(1), 1.0 / (a.std(1, unbiased=False) + 1e-8)], 1)
+
+
+def ppo_loss_rows_torch(logp_new, logp_old, values, v_old, adv, ret, stats, t0: int,
+                        entropy=None, clip=0.1, value_clip=0.1, baseline_cost=0.5,
+                        entropy_cost=0.01, step: int = 0, epoch_mean=None) -> PPOOut:
+    """``ppo_loss_torch`` on rows [t0, t0 + Tm): logp_new / values / entropy are the step's own
+    [Tm, B] arrays (g_value is [Tm, B]: no bootstrap row), logp_old / v_old / adv / ret the
+    rollout-wide ones, stats the block's pair. epoch_mean: the running mean of the epoch's
+    steps before this one (ignored at step 0); the returned one includes this step."""
+    Tm = logp_new.shape[0]
+    r = slice(t0, t0 + Tm)
+    o = ppo_loss_torch(logp_new, logp_old[r], values, v_old[r], adv[r], ret[r], stats, entropy,
+                       clip, value_clip, baseline_cost, entropy_cost)
+    mean = o.losses if step == 0 else epoch_mean + (o.losses - epoch_mean) / float(step + 1)
+    return PPOOut(o.g_logp, o.g_value, o.g_ent, o.losses, adv, ret, mean)
+
+
 def gae(v_old, reward, done, gamma=0.99, lam=0.95, reward_clip=0.0, norm_adv=True,
         ws: VTraceWorkspace | None = None) -> GaeOut:
     """v_old: [T+1, B]; reward / done: [T, B]. The outputs live in ``ws`` (reused by the next
@@ -182,3 +218,60 @@ def ppo_loss(logp_new, logp_old, values, v_old, adv, ret, stats, entropy=None, c
         baseline_cost, entropy_cost, g_logp.data_ptr(), g_value.data_ptr(), partials.data_ptr(),
         losses.data_ptr(), N.stream_ptr()), "ppo_loss")
     return PPOOut(g_logp, g_value, -entropy_cost / float(T * B), losses, adv, ret)
+
+
+def adv_stats_rows(adv, K: int, norm_adv=True, ws: VTraceWorkspace | None = None) -> torch.Tensor:
+    """adv: [T, B] (``gae``'s) -> [K, 2], the (mean, 1 / (std + 1e-8)) of each block of T / K
+    rows. One launch for all K blocks; the result lives in ``ws``."""
+    if not adv.is_cuda:
+        return adv_stats_rows_torch(adv, K, norm_adv)
+    T, B = adv.shape
+    if K < 1 or T % K != 0:
+        raise ValueError(f"ppo_minibatches {K} does not divide the {T} rows of the rollout")
+    dev = adv.device
+    ws = ws or VTraceWorkspace()
+    nb = min(256, ((T // K) * B + 255) // 256)
+    partials = ws.get("ppo_rows_stats_partials", (K * nb * 3,), dev)
+    stats = ws.get("ppo_rows_stats", (K, 2), dev)
+    ad = adv.detach().float().contiguous()
+    N.check(N.kernels().mbk_adv_stats_rows(ad.data_ptr(), T, B, K, int(bool(norm_adv)),
+                                           partials.data_ptr(), stats.data_ptr(),
+                                           N.stream_ptr()), "adv_stats_rows")
+    return stats
+
+
+def ppo_loss_rows(logp_new, logp_old, values, v_old, adv, ret, stats, t0: int, entropy=None,
+                  clip=0.1, value_clip=0.1, baseline_cost=0.5, entropy_cost=0.01, step: int = 0,
+                  epoch_mean=None, ws: VTraceWorkspace | None = None) -> PPOOut:
+    """The block form of ``ppo_loss``: logp_new / values / entropy [Tm, B] are one step's own
+    arrays over rows [t0, t0 + Tm) of the rollout; logp_old / adv / ret [>= t0 + Tm, B] and
+    v_old are the rollout-wide arrays; stats [2] is the block's pair (a row of
+    ``adv_stats_rows``). ``step`` is the step's index in its epoch: ``epoch_mean`` [7] of the
+    result is the ordered running mean of the epoch's per-step losses, kept on the device."""
+    if not logp_new.is_cuda:
+        return ppo_loss_rows_torch(logp_new, logp_old, values, v_old, adv, ret, stats, t0,
+                                   entropy, clip, value_clip, baseline_cost, entropy_cost, step,
+                                   epoch_mean)
+    Tm, B = logp_new.shape
+    if t0 < 0 or min(logp_old.shape[0], v_old.shape[0], adv.shape[0], ret.shape[0]) < t0 + Tm:
+        raise ValueError(f"rows [{t0}, {t0 + Tm}) are outside the rollout")
+    if values.numel() != Tm * B or stats.numel() != 2:
+        raise ValueError("ppo_loss_rows: values [Tm, B] and stats [2] expected")
+    dev = logp_new.device
+    ws = ws or VTraceWorkspace()
+    g_logp = ws.get("ppo_rows_g_logp", (Tm, B), dev)
+    g_value = ws.get("ppo_rows_g_value", (Tm, B), dev)
+    partials = ws.get("ppo_rows_partials", (((Tm * B + 255) // 256) * 6,), dev)
+    losses = ws.get("ppo_rows_losses", (7,), dev)
+    mean = ws.get("ppo_epoch_mean", (7,), dev)
+    c = lambda x: x.detach().float().contiguous()  # noqa: E731
+    lpn, lpo, val, vo, ad, rt, st = (c(logp_new), c(logp_old), c(values), c(v_old), c(adv),
+                                     c(ret), c(stats))
+    ent = c(entropy) if entropy is not None else None
+    N.check(N.kernels().mbk_ppo_loss_rows(
+        lpn.data_ptr(), lpo.data_ptr(), val.data_ptr(), vo.data_ptr(), ad.data_ptr(),
+        rt.data_ptr(), N.ptr(ent), st.data_ptr(), t0, Tm, B, 1.0 - clip, 1.0 + clip, clip,
+        value_clip, baseline_cost, entropy_cost, step, g_logp.data_ptr(), g_value.data_ptr(),
+        partials.data_ptr(), losses.data_ptr(), mean.data_ptr(), N.stream_ptr()),
+        "ppo_loss_rows")
+    return PPOOut(g_logp, g_value, -entropy_cost / float(Tm * B), losses, adv, ret, mean)

@@ -262,6 +262,16 @@ def all_ok(ok: bool, info: DistInfo) -> bool:
     return bool(t.item())
 
 
+def host_max(x: float, info: DistInfo) -> float:
+    """MAX of one float over the ranks, on the gloo host group like ``all_ok`` (never on the
+    RCCL group): a decision every rank must take alike, such as PPO's KL early stop."""
+    if not info.enabled:
+        return float(x)
+    t = torch.tensor([float(x)], dtype=torch.float32)
+    dist.all_reduce(t, op=dist.ReduceOp.MAX, group=info.host_group)
+    return float(t.item())
+
+
 # per-update rank states for agree(): the MIN over ranks decides what every rank does
 FAILED, RESTARTING, OK = 0, 1, 2
 

@@ -29,7 +29,7 @@ from .models.factory import make_model
 from .parallel import dist as D
 from .utils.checkpoint import (load_checkpoint, load_league_shard, restore, save_checkpoint,
                                save_league_shard)
-from .utils.metrics import PPO_LOSS_COLUMNS, CsvLogger
+from .utils.metrics import PPO_LOSS_COLUMNS, PPO_STEP_COLUMNS, CsvLogger
 
 
 def scaled_lr(flags: Flags, frames_per_update: int) -> float:
@@ -52,7 +52,11 @@ def update_frames(flags: Flags, runtime: str, world_size: int = 1) -> int:
     return flags.resolved_batch_size(runtime) * per_slot * flags.unroll_length * world_size
 
 
-def _hparams(flags: Flags, lr: float | None = None) -> LearnerHParams:
+def _hparams(flags: Flags, lr: float | None = None, rank: int = 0) -> LearnerHParams:
+    if flags.algo == "ppo" and flags.ppo_minibatches >= 1 and (
+            flags.unroll_length % flags.ppo_minibatches != 0):
+        raise ValueError(f"--ppo_minibatches {flags.ppo_minibatches} does not divide "
+                         f"--unroll_length {flags.unroll_length}")
     return LearnerHParams(lr=flags.lr if lr is None else lr, adam_eps=flags.adam_eps, gamma=flags.gamma,
                           baseline_cost=flags.baseline_cost, entropy_cost=flags.entropy_cost,
                           rho_bar=flags.rho_bar, c_bar=flags.c_bar, pg_rho_bar=flags.pg_rho_bar,
@@ -60,7 +64,9 @@ def _hparams(flags: Flags, lr: float | None = None) -> LearnerHParams:
                           bucket_mb=flags.bucket_mb, allreduce_dtype=flags.allreduce_dtype,
                           algo=flags.algo, gae_lambda=flags.gae_lambda, ppo_clip=flags.ppo_clip,
                           ppo_value_clip=flags.ppo_value_clip, ppo_epochs=flags.ppo_epochs,
-                          ppo_norm_adv=flags.ppo_norm_adv)
+                          ppo_norm_adv=flags.ppo_norm_adv,
+                          ppo_minibatches=flags.ppo_minibatches, ppo_shuffle=flags.ppo_shuffle,
+                          ppo_target_kl=flags.ppo_target_kl, ppo_seed=flags.seed + rank)
 
 
 def checkpoint_path(flags: Flags) -> str:
@@ -169,7 +175,9 @@ def resolve_runtime(flags: Flags, want_cuda: bool) -> str:
 
 
 def train(flags: Flags) -> dict:
-    _hparams(flags)  # refuses an unknown --algo / --ppo_epochs < 1 before anything starts
+    # refuses an unknown --algo, --ppo_epochs / --ppo_minibatches < 1, a --ppo_minibatches that
+    # does not divide the unroll and --ppo_target_kl < 0 before anything starts
+    _hparams(flags)
     want_cuda = flags.device == "cuda" or (flags.device == "auto" and torch.cuda.is_available())
     info = D.init_distributed(use_cuda=want_cuda, high_priority=flags.rccl_high_priority)
     dev = torch.device("cuda", info.local_rank) if want_cuda else torch.device("cpu")
@@ -211,7 +219,7 @@ def train(flags: Flags) -> dict:
     lr = scaled_lr(flags, update_frames(flags, runtime, info.world_size))
     if lr != flags.lr:
         log(f"[microbeast_amd] lr {flags.lr:g} -> {lr:g} (--lr_scaling {flags.lr_scaling})")
-    learner = Learner(model, _hparams(flags, lr), dev, info)
+    learner = Learner(model, _hparams(flags, lr, info.rank), dev, info)
     step = n_update = 0
     ck_path = checkpoint_path(flags)
     ck = None
@@ -221,8 +229,11 @@ def train(flags: Flags) -> dict:
         learner.n_updates = n_update
         log(f"[microbeast_amd] resumed {ck_path} at step={step} update={n_update}")
     ppo = flags.algo == "ppo"  # losses [7]: + approx_kl, clip_frac as trailing CSV columns
+    # minibatches / KL early stop: + the optimiser steps each rollout took
+    ppo_steps = ppo and (flags.ppo_minibatches > 1 or flags.ppo_target_kl > 0)
     logger = CsvLogger(flags.savedir, flags.exp_name, enabled=info.is_main, append=flags.resume,
-                       extra_loss_columns=PPO_LOSS_COLUMNS if ppo else ())
+                       extra_loss_columns=(PPO_LOSS_COLUMNS + (PPO_STEP_COLUMNS if ppo_steps
+                                                               else []) if ppo else ()))
 
     league = None
     if flags.self_play and runtime != "gpu":
@@ -298,7 +309,8 @@ def train(flags: Flags) -> dict:
         for lv, m in readout.pop(wait):
             logger.losses(m["update"], lv[0], lv[1], lv[2], lv[3], m["period"], m["step"],
                           m["fps"], m["wait_s"], m["learn_s"], lv[4], phase_ms=m["phase"],
-                          policy_lag=m["lag"], extra=lv[5:7] if ppo else ())
+                          policy_lag=m["lag"],
+                          extra=(lv[5:7] + ([m["opt_steps"]] if ppo_steps else [])) if ppo else ())
             last.update(update=m["update"], step=m["step"], pg_loss=lv[0], value_loss=lv[1],
                         entropy=lv[2], total_loss=lv[3], fps=m["fps"])
             log(f"update {m['update']} step {m['step']} total_loss {lv[3]:.4f} pg {lv[0]:.4f} "
@@ -397,6 +409,7 @@ def train(flags: Flags) -> dict:
                     "update": n_update, "step": step, "period": period,
                     "fps": frames_per_update / max(period, 1e-9), "wait_s": t1 - t0,
                     "learn_s": t2 - t1, "phase": learner.phases.read(), "lag": lag,
+                    "opt_steps": learner.last_opt_steps,
                     "league": (f"{len(league)} vs #{league.current}" if league is not None
                                else None)})
                 eps = rt.drain_episodes()

@@ -12,7 +12,8 @@
   update late, so logging them never synchronises the host with the GPU) and
   policy_lag (learner updates between the rollout's behaviour weights and the
   update that consumed it). ``--algo ppo`` appends approx_kl and clip_frac after them
-  (``extra_loss_columns``); the IMPALA header and rows are unchanged.
+  (``extra_loss_columns``), and opt_steps after those with ``--ppo_minibatches`` > 1 or
+  ``--ppo_target_kl`` > 0; the IMPALA header and rows are unchanged.
 
 Only rank 0 writes (DP); rows are flushed per write so a killed run keeps
 its log.
@@ -29,6 +30,8 @@ LOSS_HEADER = ["update", "pg_loss", "value_loss", "entropy_loss", "total_loss", 
                "policy_lag"]
 # --algo ppo: two more trailing columns (the mean_rho column then holds the mean ratio)
 PPO_LOSS_COLUMNS = ["approx_kl", "clip_frac"]
+# --ppo_minibatches > 1 or --ppo_target_kl > 0: the optimiser steps the rollout took, after them
+PPO_STEP_COLUMNS = ["opt_steps"]
 
 
 class PhaseTimer:

@@ -41,6 +41,10 @@ def main():
     ap.add_argument("--algo", default="impala", help="impala (V-trace) | ppo")
     ap.add_argument("--ppo_epochs", type=int, default=1,
                     help="--algo ppo: optimiser steps per update (the time printed is per update)")
+    ap.add_argument("--ppo_minibatches", type=int, default=1,
+                    help="--algo ppo: optimiser steps per epoch, each on T / K rows of the batch")
+    ap.add_argument("--ppo_target_kl", type=float, default=0.0,
+                    help="--algo ppo: > 0 reads each step's approx_kl on the host (early stop)")
     a = ap.parse_args()
     import torch
 
@@ -59,7 +63,9 @@ def main():
                          "--quiet"], interactive=False)
     torch.manual_seed(0)
     learner = Learner(make_model(flags, dev),
-                      LearnerHParams(algo=a.algo, ppo_epochs=a.ppo_epochs), dev)
+                      LearnerHParams(algo=a.algo, ppo_epochs=a.ppo_epochs,
+                                     ppo_minibatches=a.ppo_minibatches,
+                                     ppo_target_kl=a.ppo_target_kl), dev)
     S, T, B = a.size * a.size, a.T, a.batch
     g = torch.Generator(device=dev).manual_seed(1)
     # sparse legal-action masks with --active of the cells live, like the engine's rollouts
@@ -107,7 +113,8 @@ def main():
         learner.learn(batch)
     torch.cuda.synchronize()
     print(f"{(time.perf_counter() - t0) / a.steps * 1e3:.3f} ms per update "
-          f"({(T * B) / 1e3:.0f}K frames)", flush=True)
+          f"({(T * B) / 1e3:.0f}K frames, {learner.last_opt_steps} optimiser steps in the last)",
+          flush=True)
 
 
 if __name__ == "__main__":
