@@ -126,6 +126,8 @@ def test_flat_adam_kernel_vs_torch(cuda):
     for p, q in zip(mg.parameters(), ref.parameters()):
         torch.testing.assert_close(p.detach().cpu(), q.detach(), rtol=1e-4, atol=1e-5)
     torch.testing.assert_close(ag.shadow.float(), fg.data, rtol=1e-2, atol=1e-2)
+    # the shadow is the master rounded to nearest even, exactly (more: tests/test_gpu_adam.py)
+    assert torch.equal(ag.shadow.cpu(), fg.data.cpu().bfloat16())
 
 
 def test_multi_copy(cuda):

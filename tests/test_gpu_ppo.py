@@ -16,25 +16,27 @@ from ppo_cases import BC, CLIP, EC, GAMMA, LAM, VCLIP, autograd_oracle, recipe
 pytestmark = pytest.mark.gpu
 
 
-def _run_gpu(c, cuda, ws, norm=True, value_clip=VCLIP):
+def _run_gpu(c, cuda, ws, norm=True, value_clip=VCLIP, reward_clip=0.0):
     d = {k: v.to(cuda) for k, v in c.items()}
-    g = P.gae(d["v_old"], d["rew"], d["done"], GAMMA, LAM, norm_adv=norm, ws=ws)
+    g = P.gae(d["v_old"], d["rew"], d["done"], GAMMA, LAM, reward_clip=reward_clip, norm_adv=norm,
+              ws=ws)
     o = P.ppo_loss(d["lpn"], d["lpo"], d["values"], d["v_old"], g.adv, g.ret, g.stats, d["ent"],
                    clip=CLIP, value_clip=value_clip, baseline_cost=BC, entropy_cost=EC, ws=ws)
     return g, o
 
 
-def _check(c, cuda, ws, norm=True, value_clip=VCLIP):
+def _check(c, cuda, ws, norm=True, value_clip=VCLIP, reward_clip=0.0):
     """Kernels vs the fp32 torch oracle at the V-trace kernel test's tolerances; the two
     gradients are compared away from their branch boundaries (fp64 margins below 1e-4 are left
     out, at most 0.5 % of the elements)."""
     T, B = c["lpn"].shape
     M = T * B
-    rg = P.gae_torch(c["v_old"], c["rew"], c["done"], GAMMA, LAM, norm_adv=norm)
+    rg = P.gae_torch(c["v_old"], c["rew"], c["done"], GAMMA, LAM, reward_clip=reward_clip,
+                     norm_adv=norm)
     ro = P.ppo_loss_torch(c["lpn"], c["lpo"], c["values"], c["v_old"], rg.adv, rg.ret, rg.stats,
                           c["ent"], clip=CLIP, value_clip=value_clip, baseline_cost=BC,
                           entropy_cost=EC)
-    g, o = _run_gpu(c, cuda, ws, norm, value_clip)
+    g, o = _run_gpu(c, cuda, ws, norm, value_clip, reward_clip)
     adv, ret, stats = g.adv.cpu(), g.ret.cpu(), g.stats.cpu()
     torch.testing.assert_close(adv, rg.adv, rtol=1e-4, atol=1e-4)
     torch.testing.assert_close(ret, rg.ret, rtol=1e-4, atol=1e-4)
@@ -70,6 +72,22 @@ def _check(c, cuda, ws, norm=True, value_clip=VCLIP):
 ])
 def test_ppo_kernels_vs_torch(cuda, T, B, done_row, norm, value_clip):
     _check(recipe(T, B, done_row), cuda, VTraceWorkspace(), norm, value_clip)
+
+
+def test_gae_kernel_reward_clip(cuda):
+    """mbk_gae's reward clamp against gae_torch(reward_clip=0.5) (about 62 % of the unit-normal
+    rewards are clipped; on the CPU the fp64 margins of this recipe leave out 20 of the 11100
+    elements, 0.18 %, inside the 0.5 % cap), and a clip above every |r| bit-equal to no clip."""
+    c = recipe(37, 300)
+    assert 0.5 < float((c["rew"].abs() > 0.5).float().mean()) < 0.7
+    g, o = _check(c, cuda, VTraceWorkspace(), reward_clip=0.5)
+    g0, o0 = _run_gpu(c, cuda, VTraceWorkspace())
+    assert not torch.equal(g.adv, g0.adv)
+    big = float(c["rew"].abs().max()) * 1.5
+    g1, o1 = _run_gpu(c, cuda, VTraceWorkspace(), reward_clip=big)
+    for a, b in zip((g1.adv, g1.ret, g1.stats, o1.g_logp, o1.g_value, o1.losses),
+                    (g0.adv, g0.ret, g0.stats, o0.g_logp, o0.g_value, o0.losses)):
+        assert torch.equal(a, b)
 
 
 def test_ppo_kernels_are_bit_reproducible(cuda):
