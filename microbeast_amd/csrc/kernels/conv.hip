@@ -668,7 +668,7 @@ __device__ __forceinline__ void conv0_row_body(const ConvFwdArgs& a) {
       // order; the fences only keep the compiler from moving them across.
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       __builtin_amdgcn_wave_barrier();
-      const int Ho = (H + 1) >> 1, Wo = W >> 1;
+      const int Ho = (H + 1) >> 1, Wo = (W + 1) >> 1;  // (WIDE maps may be odd: 17, 19, ...)
       if (HT == 16 && !WIDE)
         pool_img16<COUT, OSTR>(otile + (size_t)wave * HW * OSTR,
                                (size_t)(img0 + wave) * Ho * Wo * COUT, a.y, a.pool_idx, lane);
@@ -1872,8 +1872,11 @@ extern "C" int mbk_conv_fwd_imgs(int in_bits, int cin, int cout, int H, int W, i
 template <int CI, int CO, bool B>
 const void* wgrad_kfn(int H, int W, bool unpool = false) {
   if (unpool) {
+    // 16 x 16 only: the kernel's scatter walks 8 x 8 windows per image (a 16-wide map of
+    // another height would read dp / pidx and write its dY tile out of bounds)
     if constexpr (CI == 32 && CO == 16 && B)
-      if (wg_band_w(H, W) == 16) return (const void*)conv_wgrad_kernel<32, 16, true, 16, true>;
+      if (H == 16 && wg_band_w(H, W) == 16)
+        return (const void*)conv_wgrad_kernel<32, 16, true, 16, true>;
     return nullptr;
   }
   switch (wg_band_w(H, W)) {
