@@ -313,7 +313,7 @@ __device__ __forceinline__ float wave_sum(float v) {
 // computed once and shared by the two windows containing the row, and the vertical pass keeps
 // the first maximising ky -- so the index is the smallest maximising tap, 6 tap reads per
 // output instead of 9. Out-of-map taps read as -inf; the centre (2 oy, 2 ox) is always inside.
-// Index maths by float reciprocals (exact: pixel counts are tiny, see conv.hip index_math_ok).
+// Index maths by float reciprocals (exact: pixel counts are tiny, see launch.h index_math_ok).
 // Shared by conv.hip (conv_fwd / conv0_row epilogues) and resblock.hip (fused stage conv).
 template <int COUT, int OSTR>
 struct PoolHRow {

@@ -29,6 +29,7 @@
 #include "../include/mbk_api.h"
 #include "common.h"
 #include "launch.h"
+#include "tile.h"
 
 #include <algorithm>
 #include <map>
@@ -39,12 +40,6 @@ using namespace mbk;
 namespace {
 
 constexpr int kThreads = 256;
-
-union Frag8 {
-  bf16x8 v;
-  uint4 u;
-  s16x4 h[2];
-};
 
 template <int CIN>
 struct Geo {
@@ -144,7 +139,7 @@ __global__ __launch_bounds__(kThreads) void conv_fwd_kernel(ConvFwdArgs a) {
   constexpr int EPP = BITS ? 1 : CIN / 8;  // staging elements per pixel (u32 / uint4)
   constexpr int OSTR = COUT + 4;           // pool staging row stride (bf16, bank spread)
   const int H = a.H, W = a.W, HW = H * W, Hp = H + 2, Wp = W + 2;
-  const float inv_hw = 1.f / (float)HW, inv_w = 1.f / (float)W;
+  const PixSplit split{HW, W, 1.f / (float)HW, 1.f / (float)W};
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, li = lane & 15;
   char* tile = smem;
@@ -256,11 +251,8 @@ __global__ __launch_bounds__(kThreads) void conv_fwd_kernel(ConvFwdArgs a) {
       const int m = pb * 16 + li;  // this lane's pixel (B column)
       const bool valid = m < M;
       const int mm = valid ? m : 0;  // rows past M compute garbage that is never stored
-      // float-reciprocal index math (exact: index_math_ok() bounds imgs*H*W at launch): the
-      // integer divisions by runtime H*W / W are ~20 VALU per block
-      const int im = (int)(((float)mm + 0.5f) * inv_hw), r = mm - im * HW;
-      const int y = (int)(((float)r + 0.5f) * inv_w), x = r - y * W;
-      const int base_pos = (im * Hp + y) * Wp + x;  // padded position of tap (0,0)
+      const Pix px = split(mm);
+      const int base_pos = (px.im * Hp + px.y) * Wp + px.x;  // padded position of tap (0,0)
       // epilogue operands (residual / relu-mask source) requested before the MFMA chain so
       // their global-load latency overlaps it instead of stalling each block's epilogue
       uint2 ep_ms[NB], ep_ad[NB];
@@ -1763,15 +1755,6 @@ int capped_resident_blocks(const void* kfn, int threads, size_t sm, int (*occ)(i
 int fwd_grid(int ngroups, const void* kfn, size_t sm) {
   const long r = (long)capped_resident_blocks(kfn, kThreads, sm, mbk_occ_f);
   return (int)std::max(1L, std::min((long)ngroups, r));
-}
-
-// The kernels map a tile-local pixel index m in [0, imgs*H*W) to (image, y, x) with float
-// reciprocals ((m + 0.5) * (1/HW)): exact while imgs*H*W < 2^22 (the product's rounding
-// error stays below the 0.5/HW distance to the next integer). LDS capacity keeps today's
-// shapes far below that; this check turns a future larger-tile / larger-map config into a
-// launch error instead of silently wrong indices.
-bool index_math_ok(int imgs, int H, int W) {
-  return H > 0 && W > 0 && H * W <= 1024 && (int64_t)imgs * H * W < (int64_t(1) << 22);
 }
 
 }  // namespace

@@ -10,6 +10,7 @@
 // fp32 partials are reduced by a deterministic two-level column sum. No host sync.
 #include "common.h"
 #include "launch.h"
+#include "tile.h"
 
 #include <cstdlib>
 
@@ -27,14 +28,8 @@ constexpr int R = 128;          // K rows per LDS stage
 constexpr int GROW = OC * 2;    // g tile row bytes
 constexpr int XROW = IC * 2;    // x tile row bytes
 
-union Frag8 {
-  bf16x8 v;
-  s16x4 h[2];
-  uint4 u;
-};
-
 // relu of 8 packed bf16 (sign bit set -> 0)
-__device__ __forceinline__ uint4 relu8(uint4 v) {
+__device__ __forceinline__ uint4 relu8_sel(uint4 v) {
   uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
   for (int j = 0; j < 4; ++j)
@@ -136,7 +131,7 @@ __global__ __launch_bounds__(kThreads) void fc_wgrad_kernel(const bf16* __restri
     for (int k = 0; k < kSPF; ++k) {
       const int e = tid + k * kThreads;
       *(uint4*)(gt + e * 16) = pg[k];
-      *(uint4*)(xt + e * 16) = xs.relu_x ? relu8(px[k]) : px[k];
+      *(uint4*)(xt + e * 16) = xs.relu_x ? relu8_sel(px[k]) : px[k];
     }
     __syncthreads();
     if (rs + R < r1) load(rs + R);
@@ -365,7 +360,7 @@ __global__ __launch_bounds__(256) void fc_fwd_rb_kernel(const bf16* __restrict__
 #pragma unroll
       for (int ks = 0; ks < NKS; ++ks) {
         uint4 v = valid ? (r ? xv1[ks] : xv0[ks]) : make_uint4(0, 0, 0, 0);
-        if (relu_in) v = relu8(v);
+        if (relu_in) v = relu8_sel(v);
         Frag8 b;
         __builtin_memcpy(&b, &v, 16);
 #pragma unroll
@@ -452,7 +447,7 @@ __global__ __launch_bounds__(64 * FW_NW, 1) void fc_wgrad_wide_kernel(
       const int e = tid + k * 64 * FW_NW, row = e / XQ, q = e % XQ;
       uint4 v = make_uint4(0, 0, 0, 0);
       if (e < FW_RS * XQ && n0 + row < N) v = ((const uint4*)(x + (size_t)(n0 + row) * I))[q];
-      px[k] = relu_x ? relu8(v) : v;
+      px[k] = relu_x ? relu8_sel(v) : v;
     }
   };
   if (s0 < s1) load(s0);

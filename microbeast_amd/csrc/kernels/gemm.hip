@@ -14,19 +14,17 @@
 // blockIdx.x walks M (the large dimension in every use) and XCD-interleaves nothing: the
 // B operand (weights) is the shared one and sits in every XCD's L2 after first touch.
 #include "common.h"
+#include "tile.h"
 
 #include <algorithm>
 
 namespace {
 
+using mbk::Frag8;
+
 constexpr int kThreads = 256;
 constexpr int TK = 32;
 constexpr int ROWB = TK * 2 + 16;  // LDS row stride (bytes): 32 bf16 + pad
-
-union Frag8 {
-  bf16x8 v;
-  uint4 u;
-};
 
 // K step TK of a ROWS-row tile = ROWS * 4 uint4; thread e moves elements e, e + 256, ...
 template <int ROWS>

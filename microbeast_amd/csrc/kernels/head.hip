@@ -35,6 +35,7 @@
 #include "../include/microrts_rules.h"
 #include "common.h"
 #include "launch.h"
+#include "tile.h"
 
 #ifndef MBK_HA_MB
 #define MBK_HA_MB 4
@@ -47,12 +48,6 @@ namespace {
 constexpr int KD = 256;      // feature width
 constexpr int NP = 80;       // 78 logits padded to 5 x 16
 constexpr int NPT = 96;      // 78 padded to 3 x 32 (K of dZ . W)
-
-union Frag8 {
-  bf16x8 v;
-  uint4 u;
-  s16x4 h[2];
-};
 
 __device__ __forceinline__ bool active3(const uint32_t* m) { return (m[0] | m[1] | m[2]) != 0u; }
 

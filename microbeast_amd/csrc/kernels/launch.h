@@ -44,6 +44,13 @@ inline int resident_blocks(const void* kfn, int threads, size_t smem, int (*occ)
   return resident_blocks(blocks_per_cu(kfn, threads, smem), occ);
 }
 
+// The tile kernels split a tile-local pixel index in [0, imgs*H*W) into (image, y, x) with
+// float reciprocals (tile.h PixSplit), exact while imgs*H*W < 2^22; every launcher of such a
+// kernel checks its round here
+inline bool index_math_ok(int imgs, int H, int W) {
+  return H > 0 && W > 0 && H * W <= 1024 && (int64_t)imgs * H * W < (int64_t(1) << 22);
+}
+
 // ------------------------------------------------------------------ weight-gradient rows
 // A conv layer's weight gradient leaves its kernel as nparts fp32 partial rows of
 // [cout][9][cin] weights + [cout] biases; the reduce (conv.hip) sums them kReducePps rows per

@@ -30,6 +30,7 @@
 // All shapes are checked on the host (mbk_pconv_* return hipErrorInvalidValue).
 #include "common.h"
 #include "launch.h"
+#include "tile.h"
 
 #include <algorithm>
 
@@ -42,13 +43,7 @@ constexpr int BK = 64;              // K step: two 32-wide MFMA K blocks
 constexpr int ROWB = BK * 2 + 16;   // LDS row bytes (16-byte pad: conflict-free b128 reads)
 constexpr int kMaxPairs = 16;
 
-union Frag8 {
-  bf16x8 v;
-  uint4 u;
-  s16x4 h[2];
-};
-
-__device__ __forceinline__ uint4 relu8(uint4 v) {
+__device__ __forceinline__ uint4 relu8_sel(uint4 v) {
   uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
   for (int j = 0; j < 4; ++j)
@@ -156,7 +151,7 @@ __device__ __forceinline__ void pconv_tile(const PConvArgs& a, char* sab, int* s
     for (int j = 0; j < AE; ++j) {
       uint4 v = make_uint4(0, 0, 0, 0);
       if (on && img[j] >= 0) v = *(const uint4*)(ap + (long long)img[j] * a.a_bs);
-      ra[j] = a.a_relu ? relu8(v) : v;
+      ra[j] = a.a_relu ? relu8_sel(v) : v;
     }
 #pragma unroll
     for (int j = 0; j < BE; ++j) {
@@ -425,7 +420,7 @@ __global__ __launch_bounds__(kThreads) void imgconv_kernel(PConvArgs a, int ntil
       const int i = rp / S::NPIX, p = rp - i * S::NPIX, m = t * S::TI + i;
       uint4 v = make_uint4(0, 0, 0, 0);
       if (m < a.M) v = *(const uint4*)(a.A + (long long)p * a.a_ps + (long long)m * a.a_bs + c8 * 8);
-      ra[j] = a.a_relu ? relu8(v) : v;
+      ra[j] = a.a_relu ? relu8_sel(v) : v;
     }
   };
   auto store = [&]() {
@@ -599,7 +594,7 @@ __global__ __launch_bounds__(kThreads) void pwgrad_kernel(PWgradArgs a) {
         const int img = rows ? a.rowimg[boff + b] : b;
         v = *(const uint4*)(xp + (long long)img * a.x_bs + c);
       }
-      px[k] = a.x_relu ? relu8(v) : v;
+      px[k] = a.x_relu ? relu8_sel(v) : v;
     }
   };
   int pr = 0, rs = b0 - WR_;
@@ -742,7 +737,7 @@ __global__ __launch_bounds__(kThreads) void pwgrad_all_kernel(PWgradAllArgs a) {
         const int b = rs + r;
         uint4 v = make_uint4(0, 0, 0, 0);
         if (ent >= 0 && b < b1 && c < a.I) v = *(const uint4*)(xp + (long long)b * a.x_bs + c);
-        px[j][k] = a.x_relu ? relu8(v) : v;
+        px[j][k] = a.x_relu ? relu8_sel(v) : v;
       }
     }
   };
@@ -866,7 +861,7 @@ __global__ __launch_bounds__(kThreads) void imgwgrad_kernel(PWgradArgs a, int nt
       const int i = r / NPIX, P = r - i * NPIX, m = tl * TI + i;
       uint4 v = m < a.M ? *(const uint4*)(a.x + (long long)P * a.x_ps + (long long)m * a.x_bs + c8 * 8)
                         : make_uint4(0, 0, 0, 0);
-      px[k] = a.x_relu ? relu8(v) : v;
+      px[k] = a.x_relu ? relu8_sel(v) : v;
     }
   };
   int tl = blockIdx.x;

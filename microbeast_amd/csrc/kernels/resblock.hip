@@ -1,27 +1,37 @@
-// Fused residual-block backward for 16-channel blocks (IMPALA stage 0: 8x8 maps at 16x16).
+// Fused residual blocks of the IMPALA trunk. Reference block (model.py:56-73):
+//   u = conv0(relu x), y = x + conv1(relu u); backward, given g = dL/dy:
+//   dW1 = relu(u) (x) g | du = conv1^T(g) * [u > 0] | dW0 = relu(x) (x) du | dx = conv0^T(du) * [x > 0] + g
+// A kernel here stages a block's tensors into halo'd LDS tiles once and keeps the intermediate
+// (relu u forward, du backward) in LDS, instead of one launch and one HBM round trip per layer.
+// Eight kernel families, two per job: a round form for any map (a workgroup takes rounds of
+// whole images, barriers between the layers; WC = the map width at compile time for the widths
+// the trunk meets, 0 = any) and a barrier-free form for the 16x16 observation's maps:
+//   res_fwd16        both 16-channel blocks of stage 0 forward (STAGE: + the next stage's conv
+//                    and pool)                                        any map but 8x8
+//   res_fwd16_w88    the same, a wave owns whole images               8x8 maps
+//   res_bwd16        one 16-channel block backward                    any map but 8x8
+//   res_bwd16_w88    the same by dgrad / weight-gradient wave pairs   8x8 maps
+//   res_blk32        one 32-channel block forward (stages 1-2)        any map
+//   res_blk32_wave   the same, a wave owns 16-pixel blocks            4x4 and 2x2 maps (own entry
+//                    point: the encoder chooses)
+//   res_bwd32        one 32-channel block backward, 8 waves           any map
+//   res_bwd32_team   the same by teams of four role waves             4x4 and 2x2 maps (own entry
+//                    point)
+// The building blocks they share (pixel split, tile window, MFMA blocks, relu gate) are tile.h's.
 //
-// Reference block (model.py:56-73): y = x + conv1(relu(conv0(relu(x)))), u = conv0(relu x).
-// Given g = dL/dy the per-layer path (ops/encoder.py) ran four launches per block, each
-// round-tripping a full activation tensor through HBM:
-//   wgrad1(relu u, g) | du = conv1^T(g) * [u > 0] | wgrad0(relu x, du) | dx = conv0^T(du) * [x > 0] + g
-// = 12 B of HBM traffic per activation byte (x, u, g read twice or more, du written and
-// re-read). Here one persistent kernel stages x, u, g of an image group into LDS once
-// (relu'd where the consumer wants relu), computes du into an LDS tile, then dx, and keeps
-// both weight gradients in MFMA accumulators for the whole launch: 4 B of HBM per
-// activation byte (read x, u, g; write dx). Profile 18 timed the four launches at ~2.3 ms
-// per block per 524K frames, near the HBM roofline for that traffic.
-//
-// MFMA mapping (v_mfma_f32_16x16x32_bf16), identical to conv.hip so dx / du are
-// bit-identical to the per-layer kernels:
-//   dgrad : A = packed transposed weights (VGPRs), B = 16 pixels x 32 K from the halo'd
-//           tile (K chunk = 2 taps x 16 channels), acc lane = 4 channels of one pixel;
+// MFMA mapping (v_mfma_f32_16x16x32_bf16), identical to conv.hip so activations and input
+// gradients are bit-identical to the per-layer kernels:
+//   conv / dgrad : A = packed (transposed) weights (VGPRs), B = 16 pixels x 32 K from the halo'd
+//           tile (16 channels: K chunk = 2 taps x 16 channels; 32: one tap), acc lane = 4
+//           channels of one pixel;
 //   wgrad : A = dY (16 co x 32 pixels) and B = X taps (32 pixels x 16 ci), both read with
 //           ds_read_b64_tr_b16 from the same halo'd tiles; acc over the 9 taps.
-// Weight grads go out as per-workgroup fp32 partial rows [2][16*144 + 16] reduced by
-// conv.hip's deterministic batched reduce (bias grads included).
+// Weight grads go out as per-workgroup fp32 partial rows (weights + bias) reduced by conv.hip's
+// deterministic batched reduce.
 #include "../include/mbk_api.h"
 #include "common.h"
 #include "launch.h"
+#include "tile.h"
 
 #include <algorithm>
 
@@ -37,16 +47,6 @@ constexpr int NCH = 5;                 // dgrad K chunks of 32 (2 taps x 16 ch; 
 constexpr int KTOT = 9 * C;            // wgrad K per output channel
 constexpr int ROW = C * KTOT + C;      // one partial row (weights + bias)
 constexpr int kPF = 2;                 // staging prefetch slots per thread per tensor (imgs*HW <= 256)
-
-union Frag8 {
-  bf16x8 v;
-  uint4 u;
-  s16x4 h[2];
-};
-
-__device__ __forceinline__ uint4 relu8(uint4 v) {
-  return make_uint4(relu2(v.x), relu2(v.y), relu2(v.z), relu2(v.w));
-}
 
 // 8x8-map tile geometry of the wave-owned kernels (res_fwd16_w88 / res_bwd16_w88): lay16(8, 8)
 namespace w88 {
@@ -89,14 +89,15 @@ __host__ __device__ inline Lay16 lay16(int H, int W) {
 template <int WC>
 __global__ __launch_bounds__(kThreads) void res_bwd16_kernel(ResBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int H = a.H, W = WC > 0 ? WC : a.W, HW = H * W, Hp = H + 2, Wp = W + 2;
-  const float inv_hw = 1.f / (float)HW, inv_w = 1.f / (float)W;
+  const int H = a.H, W = WC > 0 ? WC : a.W, HW = H * W;
+  const PixSplit split{HW, W, 1.f / (float)HW, 1.f / (float)W};
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, li = lane & 15;
   // tile layout: 8-wide maps use 32-byte pixels in 512-byte rows (no bank conflicts for the
   // dgrad ds_read_b128 or the staging writes, lay16); other widths the 48-byte pixel stride
   const Lay16 L = lay16(H, W);
   const int PB = L.pb, RB = L.rowb;
+  const TileMap T{split, PB, RB, L.imgb};
   const int tb = ((a.imgs * L.imgb) + 15) & ~15;
   char* Tg = smem;            // g          (dgrad1 input, wgrad1 dY, + g of dx)
   char* Tu = smem + tb;       // relu(u)    (wgrad1 X, du mask)
@@ -107,17 +108,9 @@ __global__ __launch_bounds__(kThreads) void res_bwd16_kernel(ResBwdArgs a) {
 
   for (int e = tid; e < (4 * tb + 64) / 16; e += kThreads) ((uint4*)smem)[e] = make_uint4(0, 0, 0, 0);
 
-  // dgrad weights (A fragments): lane holds w[co = li][chunk c][8g .. 8g+7]
-  Frag8 w1[NCH], w0[NCH];
-  {
-    const uint4* p1 = (const uint4*)(a.w1t + (size_t)li * NCH * 32 + g * 8);
-    const uint4* p0 = (const uint4*)(a.w0t + (size_t)li * NCH * 32 + g * 8);
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      w1[c].u = p1[c * 4];
-      w0[c].u = p0[c * 4];
-    }
-  }
+  Frag8 w1[NCH][1], w0[NCH][1];  // dgrad weights (A fragments)
+  load_wfrags(w1, a.w1t, li, g);
+  load_wfrags(w0, a.w0t, li, g);
   f32x4 acc1[9], acc0[9];  // wgrad accumulators, tap t: rows co = 4G + i, cols ci = li
 #pragma unroll
   for (int t = 0; t < 9; ++t) {
@@ -150,14 +143,8 @@ __global__ __launch_bounds__(kThreads) void res_bwd16_kernel(ResBwdArgs a) {
       pg[k] = ok ? ((const uint4*)a.g)[base + e] : make_uint4(0, 0, 0, 0);
     }
   };
-  auto lds_off = [&](int e) {  // staging element -> byte offset in a halo'd tile
-    const int q = e & 1, p = e >> 1;
-    const int im = (int)(((float)p + 0.5f) * inv_hw), r = p - im * HW;
-    const int y = (int)(((float)r + 0.5f) * inv_w), x = r - y * W;
-    return im * L.imgb + (y + 1) * RB + (x + 1) * PB + q * 16;
-  };
-  auto put = [&](int e, uint4 vx, uint4 vu, uint4 vg) {
-    const int o = lds_off(e);
+  auto put = [&](int e, uint4 vx, uint4 vu, uint4 vg) {  // staging element e: pixel e / 2
+    const int o = T.pixel(e >> 1) + (e & 1) * 16;
     *(uint4*)(Tx + o) = relu8(vx);
     *(uint4*)(Tu + o) = relu8(vu);
     *(uint4*)(Tg + o) = vg;
@@ -166,6 +153,32 @@ __global__ __launch_bounds__(kThreads) void res_bwd16_kernel(ResBwdArgs a) {
     for (int j = 0; j < 4; ++j) {
       db1[2 * j] += lo_f(w[j]);
       db1[2 * j + 1] += hi_f(w[j]);
+    }
+  };
+  int M, nblk, nk;
+  size_t gpix0;
+  // one layer's dgrad over the round's 16-pixel blocks: conv^T(tile S) * [mask tile Mk > 0],
+  // to Td (+ its bias sums), or (dx) + g to HBM
+  auto dgrad = [&](const Frag8(&w)[NCH][1], const char* S, const char* Mk, bool dx)
+                   __attribute__((always_inline)) {
+    for (int pb = wave; pb < nblk; pb += kThreads / 64) {
+      const int m = pb * 16 + li;
+      const bool valid = m < M;
+      const int base = T.win(valid ? m : 0);  // byte offset of tap (0, 0)
+      f32x4 acc[1];
+      conv_block16(acc, w, S + base, coff, false);
+      if (!valid) continue;
+      const int o = base + RB + PB + 4 * g * 2;  // interior pixel, channels 4g..
+      float v[4];
+      if (dx) {
+        relu_gate_add4(acc[0], *(const uint2*)(Mk + o), *(const uint2*)(Tg + o), v);
+        *(uint2*)(a.dx + (gpix0 + m) * C + 4 * g) = make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
+      } else {
+        relu_gate4(acc[0], *(const uint2*)(Mk + o), v);
+        const uint2 du = make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
+        *(uint2*)(Td + o) = du;
+        db0[0] += lo_f(du.x); db0[1] += hi_f(du.x); db0[2] += lo_f(du.y); db0[3] += hi_f(du.y);
+      }
     }
   };
 
@@ -186,128 +199,15 @@ __global__ __launch_bounds__(kThreads) void res_bwd16_kernel(ResBwdArgs a) {
     __syncthreads();
     if (rd + (int)gridDim.x < nrounds) prefetch(rd + gridDim.x);
 
-    const int M = nimg * HW, nblk = (M + 15) >> 4, nk = (M + 31) >> 5;
+    M = nimg * HW, nblk = (M + 15) >> 4, nk = (M + 31) >> 5;
+    gpix0 = (size_t)img0 * HW;
     // ---------------- phase A: du = conv1^T(g) * [u > 0] -> Td;  dW1 += relu(u) (x) g
-    for (int pb = wave; pb < nblk; pb += kThreads / 64) {
-      const int m = pb * 16 + li;
-      const bool valid = m < M;
-      const int mm = valid ? m : 0;
-      const int im = (int)(((float)mm + 0.5f) * inv_hw), r = mm - im * HW;
-      const int y = (int)(((float)r + 0.5f) * inv_w), x = r - y * W;
-      const int base = im * L.imgb + y * RB + x * PB;  // byte offset of tap (0, 0)
-      f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-      const char* bp = Tg + base;
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        Frag8 av;
-        av.u = *(const uint4*)(bp + coff[c]);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1[c].v, av.v, acc, 0, 0, 0);
-      }
-      if (!valid) continue;
-      const int o = base + RB + PB + 4 * g * 2;  // interior pixel, channels 4g..
-      const uint2 mu = *(const uint2*)(Tu + o);
-      const uint32_t mw[2] = {mu.x, mu.y};
-      float v[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const uint32_t hb = (mw[i >> 1] >> (16 * (i & 1))) & 0xFFFFu;
-        v[i] = (__uint_as_float(hb << 16) > 0.f) ? acc[i] : 0.f;
-      }
-      const uint2 du = make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
-      *(uint2*)(Td + o) = du;
-      db0[0] += lo_f(du.x); db0[1] += hi_f(du.x); db0[2] += lo_f(du.y); db0[3] += hi_f(du.y);
-    }
-    for (int kb = wave; kb < nk; kb += kThreads / 64) {
-      const char* dptr[2];
-      int xpos[2];
-      bool ok[2];
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int p = kb * 32 + 8 * g + 4 * h + (li >> 2);
-        ok[h] = p < M;
-        const int pp = ok[h] ? p : 0;
-        const int im = (int)(((float)pp + 0.5f) * inv_hw), r = pp - im * HW;
-        const int y = (int)(((float)r + 0.5f) * inv_w), x = r - y * W;
-        xpos[h] = im * L.imgb + y * RB + x * PB;  // byte offset of tap (0, 0)
-        dptr[h] = ok[h] ? Tg + xpos[h] + RB + PB : zero;
-      }
-      Frag8 af;
-#pragma unroll
-      for (int h = 0; h < 2; ++h) af.h[h] = tr_read(dptr[h] + (4 * (li & 3)) * 2);
-      // X taps: out-of-range pixels read pixel 0's (finite) values; their dY column (A)
-      // is zero, so they add exactly nothing and need no per-tap zero select
-      const char* xb0 = Tu + xpos[0] + 8 * (li & 3);
-      const char* xb1 = Tu + xpos[1] + 8 * (li & 3);
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        const int off = (t / 3) * RB + (t % 3) * PB;
-        Frag8 bf;
-        bf.h[0] = tr_read(xb0 + off);
-        bf.h[1] = tr_read(xb1 + off);
-        acc1[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af.v, bf.v, acc1[t], 0, 0, 0);
-      }
-    }
+    dgrad(w1, Tg, Tu, false);
+    for (int kb = wave; kb < nk; kb += kThreads / 64) wgrad_kblock(acc1, T, kb, M, Tg, Tu, zero);
     __syncthreads();  // Td complete
     // ---------------- phase B: dx = conv0^T(du) * [x > 0] + g -> HBM;  dW0 += relu(x) (x) du
-    const size_t gpix0 = (size_t)img0 * HW;
-    for (int pb = wave; pb < nblk; pb += kThreads / 64) {
-      const int m = pb * 16 + li;
-      const bool valid = m < M;
-      const int mm = valid ? m : 0;
-      const int im = (int)(((float)mm + 0.5f) * inv_hw), r = mm - im * HW;
-      const int y = (int)(((float)r + 0.5f) * inv_w), x = r - y * W;
-      const int base = im * L.imgb + y * RB + x * PB;
-      f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-      const char* bp = Td + base;
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        Frag8 av;
-        av.u = *(const uint4*)(bp + coff[c]);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0[c].v, av.v, acc, 0, 0, 0);
-      }
-      if (!valid) continue;
-      const int o = base + RB + PB + 4 * g * 2;
-      const uint2 mx = *(const uint2*)(Tx + o), ad = *(const uint2*)(Tg + o);
-      const uint32_t mw[2] = {mx.x, mx.y}, aw[2] = {ad.x, ad.y};
-      float v[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const uint32_t hb = (mw[i >> 1] >> (16 * (i & 1))) & 0xFFFFu;
-        v[i] = (__uint_as_float(hb << 16) > 0.f) ? acc[i] : 0.f;
-        v[i] += __uint_as_float(((aw[i >> 1] >> (16 * (i & 1))) & 0xFFFFu) << 16);
-      }
-      *(uint2*)(a.dx + (gpix0 + m) * C + 4 * g) = make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
-    }
-    for (int kb = wave; kb < nk; kb += kThreads / 64) {
-      const char* dptr[2];
-      int xpos[2];
-      bool ok[2];
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int p = kb * 32 + 8 * g + 4 * h + (li >> 2);
-        ok[h] = p < M;
-        const int pp = ok[h] ? p : 0;
-        const int im = (int)(((float)pp + 0.5f) * inv_hw), r = pp - im * HW;
-        const int y = (int)(((float)r + 0.5f) * inv_w), x = r - y * W;
-        xpos[h] = im * L.imgb + y * RB + x * PB;  // byte offset of tap (0, 0)
-        dptr[h] = ok[h] ? Td + xpos[h] + RB + PB : zero;
-      }
-      Frag8 af;
-#pragma unroll
-      for (int h = 0; h < 2; ++h) af.h[h] = tr_read(dptr[h] + (4 * (li & 3)) * 2);
-      // X taps: out-of-range pixels read pixel 0's (finite) values; their dY column (A)
-      // is zero, so they add exactly nothing and need no per-tap zero select
-      const char* xb0 = Tx + xpos[0] + 8 * (li & 3);
-      const char* xb1 = Tx + xpos[1] + 8 * (li & 3);
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        const int off = (t / 3) * RB + (t % 3) * PB;
-        Frag8 bf;
-        bf.h[0] = tr_read(xb0 + off);
-        bf.h[1] = tr_read(xb1 + off);
-        acc0[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af.v, bf.v, acc0[t], 0, 0, 0);
-      }
-    }
+    dgrad(w0, Td, Tx, true);
+    for (int kb = wave; kb < nk; kb += kThreads / 64) wgrad_kblock(acc0, T, kb, M, Td, Tx, zero);
     __syncthreads();  // tiles consumed before the next round is staged
   }
   // ---- per-workgroup partial rows: the 4 waves' accumulators summed through LDS in a fixed
@@ -490,14 +390,8 @@ __global__ __launch_bounds__(w88b::kPT) void res_bwd16_w88_kernel(ResBwdArgs a) 
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int o = j * 2 * RB + ob;
-        const uint2 mu = mus[j];
-        const uint32_t mw[2] = {mu.x, mu.y};
         float v[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const uint32_t hb = (mw[i >> 1] >> (16 * (i & 1))) & 0xFFFFu;
-          v[i] = (__uint_as_float(hb << 16) > 0.f) ? acc[j][i] : 0.f;
-        }
+        relu_gate4(acc[j], mus[j], v);
         *(uint2*)(T + TD + o) = make_uint2(cvt_pk2(v[0], v[1]), cvt_pk2(v[2], v[3]));
       }
       set_flag(f + 1, it, lane);  // du written
@@ -513,15 +407,8 @@ __global__ __launch_bounds__(w88b::kPT) void res_bwd16_w88_kernel(ResBwdArgs a) 
       char* gdx = (char*)(a.dx + (size_t)img * HW * C);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const uint2 mx = mxs[j], ad = ads[j];
-        const uint32_t mw[2] = {mx.x, mx.y}, aw[2] = {ad.x, ad.y};
         float v[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const uint32_t hb = (mw[i >> 1] >> (16 * (i & 1))) & 0xFFFFu;
-          v[i] = (__uint_as_float(hb << 16) > 0.f) ? acc[j][i] : 0.f;
-          v[i] += __uint_as_float(((aw[i >> 1] >> (16 * (i & 1))) & 0xFFFFu) << 16);
-        }
+        relu_gate_add4(acc[j], mxs[j], ads[j], v);
         *(uint2*)(gdx + j * 16 * C * 2 + goff) =
             make_uint2(cvt_pk2(v[0], v[1]), cvt_pk2(v[2], v[3]));
       }
@@ -690,8 +577,7 @@ int res_grid(int N, int H, int W, int imgs) {
 // Number of partial row PAIRS mbk_res_bwd16 writes (= its grid); <= 0: unsupported shape.
 extern "C" int mbk_res_bwd16_parts(int N, int H, int W) {
   const int imgs = res_bwd16_imgs(H, W);
-  if (N <= 0 || imgs < 1 || H * W > 1024 || (int64_t)imgs * H * W >= (int64_t(1) << 22))
-    return -1;
+  if (N <= 0 || imgs < 1 || !mbk::index_math_ok(imgs, H, W)) return -1;
   if (res_smem(imgs, H, W) > 160 * 1024) return -1;
   if ((int64_t)imgs * H * W * 2 > (int64_t)kPF * kThreads * 4) return -1;  // sane staging
   return res_grid(N, H, W, imgs);
@@ -729,23 +615,22 @@ struct ResFwdArgs {
 template <int WC, bool STAGE>
 __global__ __launch_bounds__(kThreads) void res_fwd16_kernel(ResFwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int H = a.H, W = WC > 0 ? WC : a.W, HW = H * W, Hp = H + 2, Wp = W + 2;
-  const float inv_hw = 1.f / (float)HW, inv_w = 1.f / (float)W;
+  const int H = a.H, W = WC > 0 ? WC : a.W, HW = H * W;
+  const PixSplit split{HW, W, 1.f / (float)HW, 1.f / (float)W};
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, li = lane & 15;
   const Lay16 L = lay16(H, W);  // res_bwd16's bank-conflict-free layout for 8-wide maps
   const int PB = L.pb, RB = L.rowb;
+  const TileMap T{split, PB, RB, L.imgb};
   const int tb = ((a.imgs * L.imgb) + 15) & ~15;
   char* Tx = smem;       // residual stream p -> y0 (raw)
   char* Tu = smem + tb;  // relu(u) of the current block
   for (int e = tid; e < 2 * tb / 16; e += kThreads) ((uint4*)smem)[e] = make_uint4(0, 0, 0, 0);
-  Frag8 w[4][NCH];
+  Frag8 w[4][NCH][1];
   float bv[4][4];
 #pragma unroll
   for (int l = 0; l < 4; ++l) {
-    const uint4* wp = (const uint4*)(a.w[l] + (size_t)li * NCH * 32 + g * 8);
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) w[l][c].u = wp[c * 4];
+    load_wfrags(w[l], a.w[l], li, g);
 #pragma unroll
     for (int i = 0; i < 4; ++i) bv[l][i] = a.b[l][4 * g + i];
   }
@@ -753,7 +638,7 @@ __global__ __launch_bounds__(kThreads) void res_fwd16_kernel(ResFwdArgs a) {
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
     const int tap = 2 * c + (g >> 1), tapc = tap < 9 ? tap : 8;
-    coff[c] = (tapc / 3) * RB + (tapc % 3) * PB + 16 * (g & 1);
+    coff[c] = T.tap(tapc) + 16 * (g & 1);
   }
   const int per = a.imgs * HW * 2;
   const int nrounds = (a.N + a.imgs - 1) / a.imgs;
@@ -766,12 +651,7 @@ __global__ __launch_bounds__(kThreads) void res_fwd16_kernel(ResFwdArgs a) {
       pp[k] = e < lim ? ((const uint4*)a.p)[(size_t)rd * per + e] : make_uint4(0, 0, 0, 0);
     }
   };
-  auto lds_off = [&](int e) {
-    const int q = e & 1, p = e >> 1;
-    const int im = (int)(((float)p + 0.5f) * inv_hw), r = p - im * HW;
-    const int y = (int)(((float)r + 0.5f) * inv_w), x = r - y * W;
-    return im * L.imgb + (y + 1) * RB + (x + 1) * PB + q * 16;
-  };
+  auto lds_off = [&](int e) { return T.pixel(e >> 1) + (e & 1) * 16; };  // element e: pixel e / 2
   if ((int)blockIdx.x < nrounds) prefetch(blockIdx.x);
   __syncthreads();
   for (int rd = blockIdx.x; rd < nrounds; rd += gridDim.x) {
@@ -797,27 +677,15 @@ __global__ __launch_bounds__(kThreads) void res_fwd16_kernel(ResFwdArgs a) {
         const int m = pb * 16 + li;
         const bool valid = m < M;
         const int mm = valid ? m : 0;
-        const int im = (int)(((float)mm + 0.5f) * inv_hw), r = mm - im * HW;
-        const int y = (int)(((float)r + 0.5f) * inv_w), x = r - y * W;
-        const int base = im * L.imgb + y * RB + x * PB;  // byte offset of tap (0, 0)
-        const char* bp = src + base;
-        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-          Frag8 av;
-          av.u = *(const uint4*)(bp + coff[c]);
-          if (inner) av.u = relu8(av.u);  // Tu already holds relu(u)
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[l][c].v, av.v, acc, 0, 0, 0);
-        }
+        const int base = T.win(mm);  // byte offset of tap (0, 0)
+        f32x4 acc[1];
+        conv_block16(acc, w[l], src + base, coff, inner);  // (Tu already holds relu(u))
         if (!valid) continue;
         const int o = base + RB + PB + 4 * g * 2;
         float v[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = acc[i] + bv[l][i];
-        if (!inner) {
-          const uint2 ad = *(const uint2*)(Tx + o);
-          v[0] += lo_f(ad.x); v[1] += hi_f(ad.x); v[2] += lo_f(ad.y); v[3] += hi_f(ad.y);
-        }
+        for (int i = 0; i < 4; ++i) v[i] = acc[0][i] + bv[l][i];
+        if (!inner) add_bf16x4(v, *(const uint2*)(Tx + o));
         const uint2 out = make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
         *(uint2*)(gout + (gpix0 + m) * C + 4 * g) = out;
         if (inner) *(uint2*)(Tu + o) = make_uint2(relu2(out.x), relu2(out.y));
@@ -833,32 +701,17 @@ __global__ __launch_bounds__(kThreads) void res_fwd16_kernel(ResFwdArgs a) {
       bf16* otile = (bf16*)Tu;
       Frag8 ws[NCH][NB];  // L2 reads per round (10 KB, every workgroup): keeps the persistent
       float bsv[NB][4];   // registers at the 4-layer set (occupancy 3 waves / SIMD)
+      load_wfrags(ws, a.ws, li, g);
 #pragma unroll
-      for (int nb = 0; nb < NB; ++nb) {
-        const uint4* wp = (const uint4*)(a.ws + (size_t)(nb * 16 + li) * NCH * 32 + g * 8);
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) ws[c][nb].u = wp[c * 4];
+      for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
         for (int i = 0; i < 4; ++i) bsv[nb][i] = a.bs[nb * 16 + 4 * g + i];
-      }
       for (int pb = wave; pb < nblk; pb += kThreads / 64) {
         const int m = pb * 16 + li;
         const bool valid = m < M;
         const int mm = valid ? m : 0;
-        const int im = (int)(((float)mm + 0.5f) * inv_hw), r = mm - im * HW;
-        const int y = (int)(((float)r + 0.5f) * inv_w), x = r - y * W;
-        const char* bp = Tx + im * L.imgb + y * RB + x * PB;
         f32x4 acc[NB];
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) acc[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-          Frag8 av;
-          av.u = *(const uint4*)(bp + coff[c]);
-#pragma unroll
-          for (int nb = 0; nb < NB; ++nb)
-            acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ws[c][nb].v, av.v, acc[nb], 0, 0, 0);
-        }
+        conv_block16(acc, ws, Tx + T.win(mm), coff, false);
         if (!valid) continue;
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb)
@@ -1001,10 +854,7 @@ __global__ __launch_bounds__(kThreads) void res_fwd16_w88_kernel(ResFwdArgs a) {
         float v[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = acc[j][i] + bv[l][i];
-        if (!inner) {
-          const uint2 ad = *(const uint2*)(R + TX + o);
-          v[0] += lo_f(ad.x); v[1] += hi_f(ad.x); v[2] += lo_f(ad.y); v[3] += hi_f(ad.y);
-        }
+        if (!inner) add_bf16x4(v, *(const uint2*)(R + TX + o));
         const uint2 out = make_uint2(cvt_pk2(v[0], v[1]), cvt_pk2(v[2], v[3]));
         *(uint2*)(gw + j * 16 * C * 2 + goff) = out;
         const uint2 rl = make_uint2(relu2(out.x), relu2(out.y));
@@ -1106,7 +956,8 @@ __global__ __launch_bounds__(kThreads) void res_blk32_kernel(ResBlk32Args a) {
   const int H = a.H, W = WC > 0 ? WC : a.W, HW = H * W;
   const Geo32f G3 = geo32f(H, W);
   const int PB = WC == 4 ? 64 : G3.pb, RS = WC == 4 ? 416 : G3.rs, IS = G3.is;
-  const float inv_hw = 1.f / (float)HW, inv_w = 1.f / (float)W;
+  const PixSplit split{HW, W, 1.f / (float)HW, 1.f / (float)W};
+  const TileMap T{split, PB, RS, IS};
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, li = lane & 15;
   const int tb = ((a.imgs * IS) + 15) & ~15;
@@ -1116,27 +967,20 @@ __global__ __launch_bounds__(kThreads) void res_blk32_kernel(ResBlk32Args a) {
   Frag8 w[2][NCH32][NB32];
   float bv[2][NB32][4];
 #pragma unroll
-  for (int l = 0; l < 2; ++l)
+  for (int l = 0; l < 2; ++l) {
+    load_wfrags(w[l], a.w[l], li, g);
 #pragma unroll
-    for (int nb = 0; nb < NB32; ++nb) {
-      const uint4* wp = (const uint4*)(a.w[l] + (size_t)(nb * 16 + li) * NCH32 * 32 + g * 8);
-#pragma unroll
-      for (int c = 0; c < NCH32; ++c) w[l][c][nb].u = wp[c * 4];
+    for (int nb = 0; nb < NB32; ++nb)
 #pragma unroll
       for (int i = 0; i < 4; ++i) bv[l][nb][i] = a.b[l][nb * 16 + 4 * g + i];
-    }
+  }
   int coff[NCH32];  // K chunk c = tap c, channels 8g.. of this lane
 #pragma unroll
-  for (int c = 0; c < NCH32; ++c) coff[c] = (c / 3) * RS + (c % 3) * PB + 16 * g;
+  for (int c = 0; c < NCH32; ++c) coff[c] = T.tap(c) + 16 * g;
   constexpr int EPP = C32 / 8;  // uint4 per pixel
   const int per = a.imgs * HW * EPP;
   const int nrounds = (a.N + a.imgs - 1) / a.imgs;
-  auto lds_off = [&](int e) {
-    const int q = e & (EPP - 1), p = e / EPP;
-    const int im = (int)(((float)p + 0.5f) * inv_hw), r = p - im * HW;
-    const int y = (int)(((float)r + 0.5f) * inv_w), x = r - y * W;
-    return im * IS + (y + 1) * RS + (x + 1) * PB + q * 16;
-  };
+  auto lds_off = [&](int e) { return T.pixel(e / EPP) + (e & (EPP - 1)) * 16; };
   // The next round's x is fetched into registers while this round computes (when a round
   // is at most kPF uint4 per thread), so the global-load latency leaves the critical path.
   constexpr int kPF = 4;
@@ -1177,22 +1021,9 @@ __global__ __launch_bounds__(kThreads) void res_blk32_kernel(ResBlk32Args a) {
         const int m = pb * 16 + li;
         const bool valid = m < M;
         const int mm = valid ? m : 0;
-        const int im = (int)(((float)mm + 0.5f) * inv_hw), r = mm - im * HW;
-        const int y = (int)(((float)r + 0.5f) * inv_w), x = r - y * W;
-        const int base = im * IS + y * RS + x * PB;
-        const char* bp = src + base;
+        const int base = T.win(mm);
         f32x4 acc[NB32];
-#pragma unroll
-        for (int nb = 0; nb < NB32; ++nb) acc[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < NCH32; ++c) {
-          Frag8 av;
-          av.u = *(const uint4*)(bp + coff[c]);
-          if (l == 0) av.u = relu8(av.u);  // Tu already holds relu(u)
-#pragma unroll
-          for (int nb = 0; nb < NB32; ++nb)
-            acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[l][c][nb].v, av.v, acc[nb], 0, 0, 0);
-        }
+        conv_block16(acc, w[l], src + base, coff, l == 0);  // (Tu already holds relu(u))
         if (!valid) continue;
         const int o = base + RS + PB;
 #pragma unroll
@@ -1201,10 +1032,7 @@ __global__ __launch_bounds__(kThreads) void res_blk32_kernel(ResBlk32Args a) {
           float v[4];
 #pragma unroll
           for (int i = 0; i < 4; ++i) v[i] = acc[nb][i] + bv[l][nb][i];
-          if (l == 1) {
-            const uint2 ad = *(const uint2*)(Tx + o + co0 * 2);
-            v[0] += lo_f(ad.x); v[1] += hi_f(ad.x); v[2] += lo_f(ad.y); v[3] += hi_f(ad.y);
-          }
+          if (l == 1) add_bf16x4(v, *(const uint2*)(Tx + o + co0 * 2));
           const uint2 out = make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
           *(uint2*)(gout + (gpix0 + m) * C32 + co0) = out;
           if (l == 0) *(uint2*)(Tu + o + co0 * 2) = make_uint2(relu2(out.x), relu2(out.y));
@@ -1312,10 +1140,7 @@ __global__ __launch_bounds__(rbw::kPT) void res_blk32_wave_kernel(ResBlk32Args a
         float v[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = acc[nb][i] + bv[l][nb][i];
-        if (l == 1) {
-          const uint2 ad = *(const uint2*)(Tx + pout + co0 * 2);
-          v[0] += lo_f(ad.x); v[1] += hi_f(ad.x); v[2] += lo_f(ad.y); v[3] += hi_f(ad.y);
-        }
+        if (l == 1) add_bf16x4(v, *(const uint2*)(Tx + pout + co0 * 2));
         const uint2 out = make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
         if (valid) *(uint2*)(gout + m * C32 + co0) = out;
         if (l == 0) *(uint2*)(Tu + pout + co0 * 2) = make_uint2(relu2(out.x), relu2(out.y));
@@ -1375,7 +1200,8 @@ __global__ __launch_bounds__(kT32) void res_bwd32_kernel(ResBwd32Args a) {
   const int H = a.H, W = WC > 0 ? WC : a.W, HW = H * W;
   const Geo32 G3 = geo32(H, W);
   const int PB = WC == 4 ? 64 : G3.pb, RS = WC == 4 ? 400 : G3.rs, IS = G3.is;
-  const float inv_hw = 1.f / (float)HW, inv_w = 1.f / (float)W;
+  const PixSplit split{HW, W, 1.f / (float)HW, 1.f / (float)W};
+  const TileMap T{split, PB, RS, IS};
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, li = lane & 15;
   const bool lo = wave < 4;          // waves 0-3: dgrad1 (A) + wgrad0 (B)
@@ -1391,21 +1217,13 @@ __global__ __launch_bounds__(kT32) void res_bwd32_kernel(ResBwd32Args a) {
 
   // this wave's dgrad weights (lane: rows nb * 16 + li, chunk c, elements 8g..8g+7)
   Frag8 w[NCH32][NB32];
-  {
-    const bf16* wt = lo ? a.w1t : a.w0t;
-#pragma unroll
-    for (int nb = 0; nb < NB32; ++nb) {
-      const uint4* wp = (const uint4*)(wt + (size_t)(nb * 16 + li) * NCH32 * 32 + g * 8);
-#pragma unroll
-      for (int c = 0; c < NCH32; ++c) w[c][nb].u = wp[c * 4];
-    }
-  }
+  load_wfrags(w, lo ? a.w1t : a.w0t, li, g);
   f32x4 acc[9];  // this wave's wgrad tiles (tap t): rows co = cb*16 + 4g + i, cols ci = cib*16 + li
 #pragma unroll
   for (int t = 0; t < 9; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
   int coff[NCH32];  // K chunk c = tap c, channels 8g.. of this lane
 #pragma unroll
-  for (int c = 0; c < NCH32; ++c) coff[c] = (c / 3) * RS + (c % 3) * PB + 16 * g;
+  for (int c = 0; c < NCH32; ++c) coff[c] = T.tap(c) + 16 * g;
   float db1[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // sum g: channels 8 (tid & 3) .. +8 (staging)
   float db0[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // sum du: channels nb*16 + 4g + i (waves 0-3)
 
@@ -1425,14 +1243,8 @@ __global__ __launch_bounds__(kT32) void res_bwd32_kernel(ResBwd32Args a) {
       pg[k] = ok ? ((const uint4*)a.g)[base + e] : make_uint4(0, 0, 0, 0);
     }
   };
-  auto lds_off = [&](int e) {
-    const int q = e & (EPP - 1), p = e / EPP;
-    const int im = (int)(((float)p + 0.5f) * inv_hw), r = p - im * HW;
-    const int y = (int)(((float)r + 0.5f) * inv_w), x = r - y * W;
-    return im * IS + (y + 1) * RS + (x + 1) * PB + q * 16;
-  };
-  auto put = [&](int e, uint4 vx, uint4 vu, uint4 vg) {
-    const int o = lds_off(e);
+  auto put = [&](int e, uint4 vx, uint4 vu, uint4 vg) {  // staging element e: pixel e / EPP
+    const int o = T.pixel(e / EPP) + (e & (EPP - 1)) * 16;
     *(uint4*)(Tx + o) = relu8(vx);
     *(uint4*)(Tu + o) = relu8(vu);
     *(uint4*)(Tg + o) = vg;
@@ -1443,33 +1255,36 @@ __global__ __launch_bounds__(kT32) void res_bwd32_kernel(ResBwd32Args a) {
       db1[2 * j + 1] += hi_f(wv[j]);
     }
   };
-  // wgrad K block kb (32 pixels) of this wave's tile: dY tile D (block cb), X taps from X
-  auto wgrad_kb = [&](int kb, int M, const char* D, const char* X) {
-    const char* dptr[2];
-    int xpos[2];
+  int M, nblk, nk;
+  size_t gpix0;
+  // this wave's dgrad over its 16-pixel blocks of the round: conv^T(tile S) * [mask tile Mk > 0],
+  // to Td (+ its bias sums), or (dx) + g to HBM
+  auto dgrad = [&](const char* S, const char* Mk, bool dx) __attribute__((always_inline)) {
+    for (int pb = wq; pb < nblk; pb += 4) {
+      const int m = pb * 16 + li;
+      const bool valid = m < M;
+      const int base = T.win(valid ? m : 0);
+      f32x4 ac[NB32];
+      conv_block16(ac, w, S + base, coff, false);
+      if (!valid) continue;
+      const int o = base + RS + PB;
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int p = kb * 32 + 8 * g + 4 * h + (li >> 2);
-      const bool ok = p < M;
-      const int pp = ok ? p : 0;
-      const int im = (int)(((float)pp + 0.5f) * inv_hw), r = pp - im * HW;
-      const int y = (int)(((float)r + 0.5f) * inv_w), x = r - y * W;
-      xpos[h] = im * IS + y * RS + x * PB;  // byte offset of the pixel's window top-left
-      dptr[h] = ok ? D + xpos[h] + RS + PB + cb * 32 : zero;
-    }
-    Frag8 af;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) af.h[h] = tr_read(dptr[h] + (4 * (li & 3)) * 2);
-    // out-of-range pixels read pixel 0's (finite) X values against a zero dY column
-    const char* xb0 = X + xpos[0] + cib * 32 + 8 * (li & 3);
-    const char* xb1 = X + xpos[1] + cib * 32 + 8 * (li & 3);
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-      const int off = (t / 3) * RS + (t % 3) * PB;
-      Frag8 bf;
-      bf.h[0] = tr_read(xb0 + off);
-      bf.h[1] = tr_read(xb1 + off);
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af.v, bf.v, acc[t], 0, 0, 0);
+      for (int nb = 0; nb < NB32; ++nb) {
+        const int co0 = nb * 16 + 4 * g;
+        float v[4];
+        if (dx) {
+          relu_gate_add4(ac[nb], *(const uint2*)(Mk + o + co0 * 2),
+                         *(const uint2*)(Tg + o + co0 * 2), v);
+          *(uint2*)(a.dx + (gpix0 + m) * C32 + co0) =
+              make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
+        } else {
+          relu_gate4(ac[nb], *(const uint2*)(Mk + o + co0 * 2), v);
+          const uint2 du = make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
+          *(uint2*)(Td + o + co0 * 2) = du;
+          db0[nb * 4 + 0] += lo_f(du.x); db0[nb * 4 + 1] += hi_f(du.x);
+          db0[nb * 4 + 2] += lo_f(du.y); db0[nb * 4 + 3] += hi_f(du.y);
+        }
+      }
     }
   };
 
@@ -1489,94 +1304,18 @@ __global__ __launch_bounds__(kT32) void res_bwd32_kernel(ResBwd32Args a) {
     }
     __syncthreads();
     if (rd + (int)gridDim.x < nrounds) prefetch(rd + gridDim.x);
-    const int M = nimg * HW, nblk = (M + 15) >> 4, nk = (M + 31) >> 5;
-    const size_t gpix0 = (size_t)img0 * HW;
-    // ---------------- phase A
-    if (lo) {  // du = conv1^T(g) * [u > 0]
-      for (int pb = wq; pb < nblk; pb += 4) {
-        const int m = pb * 16 + li;
-        const bool valid = m < M;
-        const int mm = valid ? m : 0;
-        const int im = (int)(((float)mm + 0.5f) * inv_hw), r = mm - im * HW;
-        const int y = (int)(((float)r + 0.5f) * inv_w), x = r - y * W;
-        const int base = im * IS + y * RS + x * PB;
-        const char* bp = Tg + base;
-        f32x4 ac[NB32];
-#pragma unroll
-        for (int nb = 0; nb < NB32; ++nb) ac[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < NCH32; ++c) {
-          Frag8 av;
-          av.u = *(const uint4*)(bp + coff[c]);
-#pragma unroll
-          for (int nb = 0; nb < NB32; ++nb)
-            ac[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[c][nb].v, av.v, ac[nb], 0, 0, 0);
-        }
-        if (!valid) continue;
-        const int o = base + RS + PB;
-#pragma unroll
-        for (int nb = 0; nb < NB32; ++nb) {
-          const int co0 = nb * 16 + 4 * g;
-          const uint2 mu = *(const uint2*)(Tu + o + co0 * 2);
-          const uint32_t mw[2] = {mu.x, mu.y};
-          float v[4];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const uint32_t hb = (mw[i >> 1] >> (16 * (i & 1))) & 0xFFFFu;
-            v[i] = (__uint_as_float(hb << 16) > 0.f) ? ac[nb][i] : 0.f;
-          }
-          const uint2 du = make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
-          *(uint2*)(Td + o + co0 * 2) = du;
-          db0[nb * 4 + 0] += lo_f(du.x); db0[nb * 4 + 1] += hi_f(du.x);
-          db0[nb * 4 + 2] += lo_f(du.y); db0[nb * 4 + 3] += hi_f(du.y);
-        }
-      }
-    } else {  // dW1 += relu(u) (x) g
-      for (int kb = 0; kb < nk; ++kb) wgrad_kb(kb, M, Tg, Tu);  // this wave's tile: every K block
-    }
+    M = nimg * HW, nblk = (M + 15) >> 4, nk = (M + 31) >> 5;
+    gpix0 = (size_t)img0 * HW;
+    // ---------------- phase A: du = conv1^T(g) * [u > 0] | dW1 += relu(u) (x) g (this wave's
+    // tile: every K block)
+    if (lo) dgrad(Tg, Tu, false);
+    else
+      for (int kb = 0; kb < nk; ++kb) wgrad_kblock(acc, T, kb, M, Tg + cb * 32, Tu + cib * 32, zero);
     __syncthreads();  // Td complete
-    // ---------------- phase B
-    if (!lo) {  // dx = conv0^T(du) * [x > 0] + g
-      for (int pb = wq; pb < nblk; pb += 4) {
-        const int m = pb * 16 + li;
-        const bool valid = m < M;
-        const int mm = valid ? m : 0;
-        const int im = (int)(((float)mm + 0.5f) * inv_hw), r = mm - im * HW;
-        const int y = (int)(((float)r + 0.5f) * inv_w), x = r - y * W;
-        const int base = im * IS + y * RS + x * PB;
-        const char* bp = Td + base;
-        f32x4 ac[NB32];
-#pragma unroll
-        for (int nb = 0; nb < NB32; ++nb) ac[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < NCH32; ++c) {
-          Frag8 av;
-          av.u = *(const uint4*)(bp + coff[c]);
-#pragma unroll
-          for (int nb = 0; nb < NB32; ++nb)
-            ac[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[c][nb].v, av.v, ac[nb], 0, 0, 0);
-        }
-        if (!valid) continue;
-        const int o = base + RS + PB;
-#pragma unroll
-        for (int nb = 0; nb < NB32; ++nb) {
-          const int co0 = nb * 16 + 4 * g;
-          const uint2 mx = *(const uint2*)(Tx + o + co0 * 2), ad = *(const uint2*)(Tg + o + co0 * 2);
-          const uint32_t mw[2] = {mx.x, mx.y}, aw[2] = {ad.x, ad.y};
-          float v[4];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const uint32_t hb = (mw[i >> 1] >> (16 * (i & 1))) & 0xFFFFu;
-            v[i] = (__uint_as_float(hb << 16) > 0.f) ? ac[nb][i] : 0.f;
-            v[i] += __uint_as_float(((aw[i >> 1] >> (16 * (i & 1))) & 0xFFFFu) << 16);
-          }
-          *(uint2*)(a.dx + (gpix0 + m) * C32 + co0) =
-              make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
-        }
-      }
-    } else {  // dW0 += relu(x) (x) du
-      for (int kb = 0; kb < nk; ++kb) wgrad_kb(kb, M, Td, Tx);
-    }
+    // ---------------- phase B: dx = conv0^T(du) * [x > 0] + g | dW0 += relu(x) (x) du
+    if (!lo) dgrad(Td, Tx, true);
+    else
+      for (int kb = 0; kb < nk; ++kb) wgrad_kblock(acc, T, kb, M, Td + cb * 32, Tx + cib * 32, zero);
     __syncthreads();  // tiles consumed before the next round is staged
   }
   // ---- partial rows: each tile straight from its owner wave (layer 1 = waves 4-7 -> block 0)
@@ -1970,8 +1709,7 @@ extern "C" int mbk_res_bwd16(const void* x, const void* u, const void* g, void* 
 // <= 0: unsupported shape.
 extern "C" int mbk_res_bwd32_parts(int N, int H, int W) {
   const int imgs = res_bwd32_imgs(H, W);
-  if (N <= 0 || imgs < 1 || H * W > 1024 || (int64_t)imgs * H * W >= (int64_t(1) << 22))
-    return -1;
+  if (N <= 0 || imgs < 1 || !mbk::index_math_ok(imgs, H, W)) return -1;
   if (res32b_smem(imgs, H, W) > 160 * 1024) return -1;
   const int nrounds = (N + imgs - 1) / imgs;
   return std::max(1, std::min(nrounds, mbk::cu_count()));
@@ -2034,8 +1772,6 @@ extern "C" int mbk_res_bwd32(const void* x, const void* u, const void* g, void* 
   return (int)hipGetLastError();
 }
 
-// One 32-channel residual block's forward (see res_blk32_kernel): u = conv0(relu x),
-// y = x + conv1(relu u), bit-identical to two conv_fwd<32, 32> launches.
 // One 32-channel residual block on 4x4 or 2x2 maps with wave-owned 16-pixel blocks
 // (res_blk32_wave_kernel): bit-identical to mbk_res_blk32_fwd.
 extern "C" int mbk_res_blk32_fwd_wave(const void* x, void* u, void* y, const void* const* w,
@@ -2064,13 +1800,14 @@ extern "C" int mbk_res_blk32_fwd_wave(const void* x, void* u, void* y, const voi
   return (int)hipGetLastError();
 }
 
+// One 32-channel residual block's forward (see res_blk32_kernel): u = conv0(relu x),
+// y = x + conv1(relu u), bit-identical to two conv_fwd<32, 32> launches.
 extern "C" int mbk_res_blk32_fwd(const void* x, void* u, void* y, const void* const* w,
                                  const float* const* b, int N, int H, int W,
                                  hipStream_t stream) {
   if (N <= 0) return 0;
   const int imgs = res_blk32_imgs(H, W);
-  if (imgs < 1 || H * W > 1024 || (int64_t)imgs * H * W >= (int64_t(1) << 22))
-    return (int)hipErrorInvalidValue;
+  if (imgs < 1 || !mbk::index_math_ok(imgs, H, W)) return (int)hipErrorInvalidValue;
   const size_t sm = resb32_smem(imgs, H, W);
   if (sm > 160 * 1024) return (int)hipErrorInvalidValue;
   ResBlk32Args a{(const bf16*)x, (bf16*)u, (bf16*)y, {(const bf16*)w[0], (const bf16*)w[1]},

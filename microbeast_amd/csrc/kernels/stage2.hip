@@ -17,17 +17,13 @@
 #include "../include/mbk_api.h"
 #include "common.h"
 #include "launch.h"
+#include "tile.h"
 
 #include <algorithm>
 
 using namespace mbk;
 
 namespace {
-
-union Frag8 {
-  bf16x8 v;
-  uint4 u;
-};
 
 namespace s2 {
 constexpr int H = 4, W = 4, HW = 16, C = 32, HO = 2, WO = 2;

@@ -29,18 +29,13 @@
 #include "../include/mbk_api.h"
 #include "common.h"
 #include "launch.h"
+#include "tile.h"
 
 #include <algorithm>
 
 using namespace mbk;
 
 namespace {
-
-union Frag8 {
-  bf16x8 v;
-  uint4 u;
-  s16x4 h[2];
-};
 
 // ---- geometry (stage 1 at 16x16): x 8x8x16, dc 8x8x32, pooled 4x4x32
 namespace s1 {

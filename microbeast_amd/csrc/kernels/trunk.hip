@@ -22,6 +22,7 @@
 #include "../include/mbk_api.h"
 #include "common.h"
 #include "launch.h"
+#include "tile.h"
 #include "decode.h"
 
 
@@ -36,11 +37,6 @@ namespace {
 constexpr int kThreads = 512;  // 8 waves: 2 per SIMD even at one workgroup per CU
 constexpr int kMaxTNI = 16;  // images per workgroup iteration (host picks <= this)
 constexpr int kWBufBytes = 32 * (9 * 64 + 16);  // one staged layer (largest: 32x32)
-
-union Frag8 {
-  bf16x8 v;
-  uint4 u;
-};
 
 template <int C>
 struct TG {
@@ -226,12 +222,11 @@ __device__ __forceinline__ void conv_lds(int in, int H, int W, int nimg, int lw_
   // distance of (m + 0.5) / HW to an integer is >= 0.5 / HW, far above the rounding error;
   // mbk_trunk_tail refuses shapes outside that bound);
   // the integer divisions by runtime H*W / W cost ~20 VALU per block (profile 15: VALU-bound)
-  const float inv_hw = 1.f / (float)HW, inv_w = 1.f / (float)W;
+  const PixSplit split{HW, W, 1.f / (float)HW, 1.f / (float)W};
   auto epilogue = [&](int pb, const f32x4* acc) {
     const int m = pb * 16 + li;
     if (pb >= nblk || m >= M) return;
-    const int im = (int)(((float)m + 0.5f) * inv_hw), r = m - im * HW;
-    const int y = (int)(((float)r + 0.5f) * inv_w), x = r - y * W;
+    const Pix px = split(m);
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       const int co0 = nb * 16 + 4 * g;
@@ -241,7 +236,7 @@ __device__ __forceinline__ void conv_lds(int in, int H, int W, int nimg, int lw_
         if constexpr (F8) v[i] = acc[nb][i] * wsc[nb][i] + bv[nb][i];
         else v[i] = acc[nb][i] + bv[nb][i];
       }
-      const int pix = (im * Hp + y + 1) * Wp + x + 1;
+      const int pix = (px.im * Hp + px.y + 1) * Wp + px.x + 1;
       if constexpr (MODE == OUT_STAGE) {
         *(uint2*)(trunk_smem + out + (m * COUT + co0) * 2) =
             make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
@@ -271,9 +266,8 @@ __device__ __forceinline__ void conv_lds(int in, int H, int W, int nimg, int lw_
     for (int j = 0; j < NJ; ++j) {
       const int m = (pb0 + j * poff) * 16 + li;
       const int mm = m < M ? m : 0;  // rows past M compute garbage that is never stored
-      const int im = (int)(((float)mm + 0.5f) * inv_hw), r = mm - im * HW;
-      const int y = (int)(((float)r + 0.5f) * inv_w), x = r - y * W;
-      base[j] = in + ((im * Hp + y) * Wp + x) * PI;
+      const Pix px = split(mm);
+      base[j] = in + ((px.im * Hp + px.y) * Wp + px.x) * PI;
     }
     f32x4 acc[2][NB];
 #pragma unroll
@@ -494,7 +488,7 @@ __device__ __forceinline__ int tail_n16(int l) {
          tail_cout(l) * TG<32>::NCH * 4 * (tail_cin(l) == 32 ? 1 : 0);
 }
 
-__device__ __forceinline__ uint4 relu8(uint4 v) {
+__device__ __forceinline__ uint4 relu8_sel(uint4 v) {
   uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
   for (int j = 0; j < 4; ++j)
@@ -529,7 +523,7 @@ __device__ __forceinline__ void trunk_fc(const char* x2, int H2, int W2, int nim
         Frag8 b, w;
         b.u = make_uint4(0, 0, 0, 0);
         if (valid)
-          b.u = relu8(*(const uint4*)(x2 + ((im * (H2 + 2) + py + 1) * (W2 + 2) + px + 1) * PX +
+          b.u = relu8_sel(*(const uint4*)(x2 + ((im * (H2 + 2) + py + 1) * (W2 + 2) + px + 1) * PX +
                                       G * 16));
         w.u = wrow[ks * 4];
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.v, b.v, acc, 0, 0, 0);
@@ -991,7 +985,7 @@ __device__ __forceinline__ void tile_fc(int nimg, int img0, const TrunkArgs& a,
 #pragma unroll
   for (int ks = 0; ks < NKS; ++ks) {
     const int py = ks / W2, px = ks - py * W2;
-    b[ks].u = valid ? relu8(*(const uint4*)(trunk_smem + x2 + ((py + 1) * (W2 + 2) + px + 1) * PX +
+    b[ks].u = valid ? relu8_sel(*(const uint4*)(trunk_smem + x2 + ((py + 1) * (W2 + 2) + px + 1) * PX +
                                             G * 16))
                     : make_uint4(0, 0, 0, 0);
   }

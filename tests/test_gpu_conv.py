@@ -482,7 +482,7 @@ def test_conv0_row_kernel_bit_identical_to_generic(cuda, n, pool, cout, s):
                                    atol=2e-2)
 
 
-@pytest.mark.parametrize("s,n", [(16, 37), (10, 21), (24, 5)])
+@pytest.mark.parametrize("s,n", [(16, 37), (10, 21), (24, 5), (18, 5)])
 def test_fused_res_bwd16_matches_per_layer_kernels(cuda, s, n):
     """resblock.hip (one launch per 16-channel residual block backward) against the four
     per-layer kernels: the input gradients flowing on are bit-identical (same MFMA chains,
@@ -615,7 +615,7 @@ def test_batched_deferred_reduce_bit_identical(cuda, n, fused):
         assert torch.equal(a, b), i
 
 
-@pytest.mark.parametrize("s,n", [(16, 37), (10, 21)])
+@pytest.mark.parametrize("s,n", [(16, 37), (10, 21), (18, 5)])
 def test_fused_res_fwd16_bit_identical(cuda, s, n):
     """resblock.hip res_fwd16 (both 16-channel residual blocks in one launch) writes the
     same u0 / y0 / u1 / y1 bits as four conv_fwd launches."""
@@ -712,7 +712,7 @@ def test_res_blk32_wave_bit_identical(cuda, s, n):
         assert torch.equal(a, b), i
 
 
-@pytest.mark.parametrize("s,n", [(16, 37), (10, 21), (24, 9)])
+@pytest.mark.parametrize("s,n", [(16, 37), (10, 21), (24, 9), (18, 5)])
 def test_fused_res_blk32_bit_identical(cuda, s, n):
     """resblock.hip res_blk32 (one 32-channel residual block per launch, weights of both
     layers in registers) writes the same bits for every saved activation as the per-layer
@@ -771,7 +771,7 @@ def test_res_bwd32_team_matches_round_kernel(cuda, s, n):
             assert torch.equal(a, b), i
 
 
-@pytest.mark.parametrize("s,n", [(16, 37), (10, 21), (24, 9)])
+@pytest.mark.parametrize("s,n", [(16, 37), (10, 21), (24, 9), (18, 5)])
 def test_fused_res_bwd32_matches_per_layer_kernels(cuda, s, n):
     """resblock.hip res_bwd32 (one 8-wave launch per 32-channel residual block backward)
     against the per-layer wgrad / dgrad kernels: input gradients flowing on are
