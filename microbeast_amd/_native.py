@@ -70,6 +70,9 @@ _SIGS = {
                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "mbk_gae": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_float, c_int,
                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "mbk_vtrace_adv": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,
+                       c_float, c_float, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p,
+                       c_void_p, c_void_p, c_void_p],
     "mbk_ppo_loss": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                      c_void_p, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float,
                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],

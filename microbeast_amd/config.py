@@ -64,6 +64,9 @@ class Flags:
     ppo_shuffle: bool = True      # ppo: visit the K blocks in a fresh random order each epoch
     ppo_target_kl: float = 0.0    # ppo: > 0: no further optimiser step on a rollout once a
                                   # step's approx_kl exceeds it (that step is applied); 0 = off
+    ppo_adv: str = "gae"          # ppo: gae | vtrace: advantages and value targets from a
+                                  # V-trace(lambda) scan clipped by --rho_bar / --c_bar, for
+                                  # rollouts acted by lagged weights (GAE when on-policy)
     # --- environment
     env: str = "synthetic"        # synthetic | microrts (gym-microrts adapter, if installed)
     opponents: str = "coac,coac,coac,random_biased,light_rush,worker_rush"

@@ -119,6 +119,17 @@ int mbk_act_head(const MbkActModel* m, const MbkActStep* s, hipStream_t stream);
 int mbk_gae(const float* v_old, const float* reward, const uint8_t* done, int T, int B,
             float gamma, float lambda, float reward_clip, int norm_adv, float* adv, float* ret,
             float* partials, float* stats, hipStream_t stream);
+// mbk_gae corrected for a rollout acted by an older policy (V-trace(lambda)): logp_pi [T, B] are
+// the log-probs of the pass that gave v, logp_mu the behaviour ones, w = exp(logp_pi - logp_mu).
+//   adv_t = td_t + gamma nd_t lambda d_{t+1},  d_t = min(rho_bar, w_t) td_t
+//           + gamma nd_t lambda min(c_bar, w_t) d_{t+1}  (d_T = 0),  ret_t = v[t] + d_t
+// is_stats[3] = mean w, share of w > rho_bar, share of w > c_bar. Both bars > 0.
+// partials: 6 * ceil(B / 256) floats. Ordered, no atomics.
+int mbk_vtrace_adv(const float* logp_pi, const float* logp_mu, const float* v,
+                   const float* reward, const uint8_t* done, int T, int B, float gamma,
+                   float lambda, float rho_bar, float c_bar, float reward_clip, int norm_adv,
+                   float* adv, float* ret, float* partials, float* stats, float* is_stats,
+                   hipStream_t stream);
 // Clipped surrogate + clipped value loss and their gradients g_logp [T, B], g_value [T+1, B]
 // (row T zeroed); losses[7] = pg, value, entropy, total, mean ratio, approx_kl, clip_frac.
 // clip_lo / clip_hi = 1 -/+ clip as the caller rounds them; value_clip 0 = unclipped value

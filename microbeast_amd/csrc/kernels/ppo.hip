@@ -9,6 +9,12 @@
 //     delta_t = r_t + gamma nd_t v_old[t+1] - v_old[t],  A_t = delta_t + gamma lambda nd_t A_{t+1}
 //     (A_T = 0),  R_t = A_t + v_old[t];  stats = (mean A, 1 / (std A + 1e-8)) over the T*B
 //     elements (population std), or (0, 1) with normalisation off.
+//   mbk_vtrace_adv  mbk_gae for rollouts acted by an older policy mu (--ppo_adv vtrace):
+//     + logp_pi, logp_mu [T,B] -> adv, ret, stats as above, is_stats[3]
+//     w = exp(logp_pi - logp_mu), rho = min(rho_bar, w), c = lambda min(c_bar, w)
+//     adv_t = delta_t + gamma nd_t lambda d_{t+1},  d_t = rho_t delta_t + gamma nd_t c_t d_{t+1}
+//     (d_T = 0),  ret_t = v_old[t] + d_t;  is_stats = mean w, share w > rho_bar, share w > c_bar.
+//     w == 1 and both bars >= 1: mbk_gae's adv and ret.
 //   mbk_ppo_loss  logp_new, logp_old, v, v_old, adv, ret, entropy, stats -> g_logp [T,B],
 //     g_value [T+1,B] (row T = 0), losses[7]
 //     A^ = (A - mean) rstd, ratio = exp(logp_new - logp_old), M = T*B
@@ -117,6 +123,99 @@ __global__ __launch_bounds__(64) void gae_finalize_kernel(const float* __restric
     const float sd = sqrtf(fmaxf(s.m2, 0.f) / fmaxf(s.n, 1.f));
     stats[0] = norm ? s.mean : 0.f;
     stats[1] = norm ? 1.f / (sd + 1e-8f) : 1.f;
+  }
+}
+
+// V-trace(lambda) advantages for lagged rollouts: gae_kernel with the importance weights
+// w = exp(logp_pi - logp_mu) of the learner's first pass against the behaviour policy.
+// d = vs - v is the carried value; with w == 1 and both bars >= 1 every step is gae_kernel's.
+// partials [gridDim.x][kVtParts] = the block's (n, mean, M2) of adv, then its sums of w,
+// (w > rho_bar) and (w > c_bar).
+constexpr int kVtParts = 6;
+
+__global__ __launch_bounds__(256) void vtrace_adv_kernel(
+    const float* __restrict__ logp_pi, const float* __restrict__ logp_mu,
+    const float* __restrict__ v_old, const float* __restrict__ reward,
+    const uint8_t* __restrict__ done, int T, int B, float gamma, float lambda, float rho_bar,
+    float c_bar, float reward_clip, float* __restrict__ adv_out, float* __restrict__ ret_out,
+    float* __restrict__ partials) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  Moments mo = {0.f, 0.f, 0.f};
+  float is[3] = {0.f, 0.f, 0.f};
+  if (b < B) {
+    float v_next = v_old[(size_t)T * B + b];
+    float acc = 0.f;  // d_{t+1}
+    for (int t = T - 1; t >= 0; --t) {
+      const size_t i = (size_t)t * B + b;
+      const float w = __expf(logp_pi[i] - logp_mu[i]);
+      float r = reward[i];
+      if (reward_clip > 0.f) r = fmaxf(-reward_clip, fminf(reward_clip, r));
+      const float disc = done[i] ? 0.f : gamma;
+      const float v = v_old[i];
+      const float delta = r + disc * v_next - v;
+      const float a = delta + disc * lambda * acc;
+      acc = fminf(rho_bar, w) * delta + disc * (lambda * fminf(c_bar, w)) * acc;
+      adv_out[i] = a;
+      ret_out[i] = acc + v;
+      mo.n += 1.f;
+      const float d = a - mo.mean;
+      mo.mean += d / mo.n;
+      mo.m2 += d * (a - mo.mean);
+      is[0] += w;
+      is[1] += w > rho_bar ? 1.f : 0.f;
+      is[2] += w > c_bar ? 1.f : 0.f;
+      v_next = v;
+    }
+  }
+  __shared__ Moments red[4];
+  __shared__ float red_is[4][3];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  mo = wave_merge(mo);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) is[k] = wave_sum(is[k]);
+  if (lane == 0) {
+    red[wave] = mo;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) red_is[wave][k] = is[k];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    Moments s = red[0];
+    float t[3] = {red_is[0][0], red_is[0][1], red_is[0][2]};
+    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) {
+      s = merge(s, red[w]);
+      for (int k = 0; k < 3; ++k) t[k] += red_is[w][k];
+    }
+    float* out = partials + (size_t)blockIdx.x * kVtParts;
+    out[0] = s.n;
+    out[1] = s.mean;
+    out[2] = s.m2;
+    out[3] = t[0];
+    out[4] = t[1];
+    out[5] = t[2];
+  }
+}
+
+// gae_finalize_kernel's stats, and is_stats[0..2] = mean w, share of w > rho_bar, share of
+// w > c_bar over the M = T*B elements
+__global__ __launch_bounds__(64) void vtrace_adv_finalize_kernel(
+    const float* __restrict__ partials, int nblocks, int norm, float invM,
+    float* __restrict__ stats, float* __restrict__ is_stats) {
+  const int lane = threadIdx.x;
+  Moments s = {0.f, 0.f, 0.f};
+  float t[3] = {0.f, 0.f, 0.f};
+  for (int i = lane; i < nblocks; i += 64) {
+    const float* p = partials + (size_t)i * kVtParts;
+    s = merge(s, Moments{p[0], p[1], p[2]});
+    for (int k = 0; k < 3; ++k) t[k] += p[3 + k];
+  }
+  s = wave_merge(s);
+  for (int k = 0; k < 3; ++k) t[k] = wave_sum(t[k]);
+  if (lane == 0) {
+    const float sd = sqrtf(fmaxf(s.m2, 0.f) / fmaxf(s.n, 1.f));
+    stats[0] = norm ? s.mean : 0.f;
+    stats[1] = norm ? 1.f / (sd + 1e-8f) : 1.f;
+    for (int k = 0; k < 3; ++k) is_stats[k] = t[k] * invM;
   }
 }
 
@@ -383,6 +482,22 @@ extern "C" int mbk_gae(const float* v_old, const float* reward, const uint8_t* d
                      lambda, reward_clip, adv, ret, partials);
   hipLaunchKernelGGL(gae_finalize_kernel, dim3(1), dim3(64), 0, stream, partials, nb, norm_adv,
                      stats);
+  return (int)hipGetLastError();
+}
+
+// partials: 6 * ceil(B / 256) floats; stats[2]; is_stats[3]
+extern "C" int mbk_vtrace_adv(const float* logp_pi, const float* logp_mu, const float* v,
+                              const float* reward, const uint8_t* done, int T, int B, float gamma,
+                              float lambda, float rho_bar, float c_bar, float reward_clip,
+                              int norm_adv, float* adv, float* ret, float* partials, float* stats,
+                              float* is_stats, hipStream_t stream) {
+  if (T < 1 || B < 1 || !(rho_bar > 0.f) || !(c_bar > 0.f)) return (int)hipErrorInvalidValue;
+  const int nb = (B + 255) / 256;
+  hipLaunchKernelGGL(vtrace_adv_kernel, dim3(nb), dim3(256), 0, stream, logp_pi, logp_mu, v,
+                     reward, done, T, B, gamma, lambda, rho_bar, c_bar, reward_clip, adv, ret,
+                     partials);
+  hipLaunchKernelGGL(vtrace_adv_finalize_kernel, dim3(1), dim3(64), 0, stream, partials, nb,
+                     norm_adv, 1.f / ((float)T * (float)B), stats, is_stats);
   return (int)hipGetLastError();
 }
 

@@ -23,9 +23,9 @@ from dataclasses import dataclass
 
 import torch
 
-from .ops.copy import full
+from .ops.copy import full, multi_copy
 from .ops.optim import FlatAdam, FlatParams
-from .ops.ppo import adv_stats_rows, gae, ppo_loss, ppo_loss_rows
+from .ops.ppo import adv_stats_rows, gae, ppo_loss, ppo_loss_rows, vtrace_adv
 from .ops.vtrace import VTraceWorkspace, vtrace
 from .parallel.dist import DistInfo, GradAllReducer, broadcast_flat, host_max
 from .utils.metrics import PhaseTimer
@@ -56,10 +56,16 @@ class LearnerHParams:
     ppo_shuffle: bool = True       # ppo: visit the K row blocks in a fresh order each epoch
     ppo_target_kl: float = 0.0     # ppo: > 0 ends the rollout's steps after one exceeds it
     ppo_seed: int = 0              # ppo: seeds the block orders (with n_updates and the epoch)
+    ppo_adv: str = "gae"           # ppo: gae | vtrace (rho_bar / c_bar-clipped, ops/ppo.py)
 
     def __post_init__(self):
         if self.algo not in ("impala", "ppo"):
             raise ValueError(f"--algo {self.algo!r}: expected impala | ppo")
+        if self.ppo_adv not in ("gae", "vtrace"):
+            raise ValueError(f"--ppo_adv {self.ppo_adv!r}: expected gae | vtrace")
+        if self.ppo_adv == "vtrace" and not (self.rho_bar > 0 and self.c_bar > 0):
+            raise ValueError(f"--ppo_adv vtrace: --rho_bar {self.rho_bar} / --c_bar {self.c_bar}: "
+                             "expected > 0")
         if self.ppo_epochs < 1:
             raise ValueError(f"--ppo_epochs {self.ppo_epochs}: expected >= 1")
         if self.ppo_minibatches < 1:
@@ -98,6 +104,9 @@ class Learner:
         self.ws = VTraceWorkspace()
         self.n_updates = 0
         self.last_opt_steps = 0  # optimiser steps applied in the last learn()
+        # ppo_adv="vtrace": device tensor [3] = mean importance weight, share above rho_bar,
+        # share above c_bar of the last rollout (ops/ppo.py)
+        self.last_is_stats = None
         self.timing = {}
         # HIP-event split fwd / bwd / allreduce(wait) / optim (+ publish marked by the
         # caller), read one update late without a host sync
@@ -163,7 +172,9 @@ class Learner:
         clipped losses -> backward -> all-reduce -> Adam, so Adam's step count advances once
         per epoch while ``n_updates`` counts rollouts. Epoch 0 snapshots its own values as
         ``v_old`` and runs GAE on them (ops/ppo.py); later epochs reuse adv / ret / stats /
-        v_old from the workspace. Under data parallelism the advantages are normalised with
+        v_old from the workspace. ``ppo_adv="vtrace"``: epoch 0 snapshots its own log-probs as
+        well and runs the V-trace(lambda) scan in GAE's place (``_vtrace_adv``), for rollouts
+        acted by lagged weights. Under data parallelism the advantages are normalised with
         each rank's own statistics. Returns the last epoch's device tensor [7] = pg, value,
         entropy, total, mean ratio, approx_kl, clip_frac; nothing syncs the host.
         ``ppo_minibatches`` > 1 or ``ppo_target_kl`` > 0: ``_learn_ppo_steps`` instead."""
@@ -190,7 +201,9 @@ class Learner:
             self.flat.zero_grad()
             self.reducer.start_step()
             logp, ent, value = self.model.evaluate(flat_obs, m, a, n_score=T * B, **kw)
-            if epoch == 0:
+            if epoch == 0 and hp.ppo_adv == "vtrace":
+                v_old, g = self._vtrace_adv(batch, value, logp, T1, B, cuda)
+            elif epoch == 0:
                 if cuda:  # (a workspace buffer: the forward's own output is rewritten per epoch)
                     v_old = self.ws.get("ppo_v_old", (T1, B), value.device)
                     v_old.copy_(value.detach().view(T1, B))
@@ -238,7 +251,9 @@ class Learner:
         K blocks of T / K consecutive rows (all envs) once, in ``ppo_block_order``'s order, and
         each visit is a full optimiser step on that block alone: zero grads -> forward on the
         block's rows (no bootstrap row) -> block loss -> backward -> all-reduce -> Adam. K == 1
-        keeps ``_learn_ppo``'s steps (epoch 0's own values are ``v_old``).
+        keeps ``_learn_ppo``'s steps (epoch 0's own values are ``v_old``). ``ppo_adv="vtrace"``:
+        the pre-pass is a no-grad ``evaluate`` over the slot, whose log-probs the V-trace(lambda)
+        scan needs beside the values (``_vtrace_adv``).
 
         ``ppo_target_kl`` > 0: the host reads a step's approx_kl only AFTER that step's
         backward, all-reduce and Adam are queued (an event recorded behind the loss launch and
@@ -272,15 +287,20 @@ class Learner:
         g = v_old = stats = mean = None
         if K > 1:
             args, kw = rows(0, T, T1)
-            with torch.no_grad():
-                if hasattr(self.model, "values"):
-                    v = self.model.values(args[0])
-                else:
-                    v = self.model.evaluate(*args, n_score=T * B, **kw)[2]
-            v_old = self._snapshot_values(v, T1, B, cuda)
-            g = gae(v_old, batch["reward"][:T], batch["done"][:T], gamma=hp.gamma,
-                    lam=hp.gae_lambda, reward_clip=hp.reward_clip, norm_adv=hp.ppo_norm_adv,
-                    ws=self.ws)
+            if hp.ppo_adv == "vtrace":  # the scan needs the pass's log-probs too
+                with torch.no_grad():
+                    lp, _, v = self.model.evaluate(*args, n_score=T * B, **kw)
+                v_old, g = self._vtrace_adv(batch, v, lp, T1, B, cuda)
+            else:
+                with torch.no_grad():
+                    if hasattr(self.model, "values"):
+                        v = self.model.values(args[0])
+                    else:
+                        v = self.model.evaluate(*args, n_score=T * B, **kw)[2]
+                v_old = self._snapshot_values(v, T1, B, cuda)
+                g = gae(v_old, batch["reward"][:T], batch["done"][:T], gamma=hp.gamma,
+                        lam=hp.gae_lambda, reward_clip=hp.reward_clip,
+                        norm_adv=hp.ppo_norm_adv, ws=self.ws)
             stats = adv_stats_rows(g.adv, K, hp.ppo_norm_adv, ws=self.ws)
         steps, stop = 0, False
         for epoch in range(hp.ppo_epochs):
@@ -292,7 +312,9 @@ class Learner:
                 if K == 1:
                     args, kw = rows(0, T, T1)
                     logp, ent, value = self.model.evaluate(*args, n_score=T * B, **kw)
-                    if epoch == 0:
+                    if epoch == 0 and hp.ppo_adv == "vtrace":
+                        v_old, g = self._vtrace_adv(batch, value, logp, T1, B, cuda)
+                    elif epoch == 0:
                         v_old = self._snapshot_values(value, T1, B, cuda)
                         g = gae(v_old, batch["reward"][:T], batch["done"][:T], gamma=hp.gamma,
                                 lam=hp.gae_lambda, reward_clip=hp.reward_clip,
@@ -355,6 +377,27 @@ class Learner:
             v_old.copy_(value.detach().view(T1, B))
             return v_old
         return value.detach().float().view(T1, B).clone()
+
+    def _vtrace_adv(self, batch: dict, value: torch.Tensor, logp: torch.Tensor, T1: int, B: int,
+                    cuda: bool):
+        """``ppo_adv="vtrace"``: snapshot one pass's values [T1, B] and log-probs [T, B] (on a
+        GPU: workspace buffers filled by one copy launch) and run the V-trace(lambda) scan on
+        them against the batch's behaviour log-probs. Returns (v_old, GaeOut); keeps the
+        importance statistics as ``last_is_stats``."""
+        hp, T = self.hp, T1 - 1
+        if cuda:
+            v_old = self.ws.get("ppo_v_old", (T1, B), value.device)
+            logp_pi = self.ws.get("ppo_logp_pi", (T, B), value.device)
+            multi_copy([(value.detach().float().contiguous(), v_old),
+                        (logp.detach().float().contiguous(), logp_pi)])
+        else:
+            v_old = value.detach().float().view(T1, B).clone()
+            logp_pi = logp.detach().float().view(T, B).clone()
+        g, self.last_is_stats = vtrace_adv(
+            logp_pi, batch["logp"][:T], v_old, batch["reward"][:T], batch["done"][:T],
+            gamma=hp.gamma, lam=hp.gae_lambda, rho_bar=hp.rho_bar, c_bar=hp.c_bar,
+            reward_clip=hp.reward_clip, norm_adv=hp.ppo_norm_adv, ws=self.ws)
+        return v_old, g
 
     def _kl_record(self, losses: torch.Tensor):
         """Right behind a step's loss launch: queue the 4-byte copy of its approx_kl into pinned

@@ -23,6 +23,24 @@ same on both runtimes.
               ``norm_adv`` off. Under data parallelism each rank normalises with its own
               batch's statistics (no collective).
 
+``vtrace_adv`` (``--ppo_adv vtrace``) takes ``gae``'s place when the rollout was acted by an
+older policy mu, as the asynchronous actors' rollouts are: ``gae`` is unbiased only for
+pi = mu. It is a V-trace(lambda) reverse scan (Espeholt et al. 2018, with lambda folded into
+the trace) on the same value snapshot ``v`` = ``v_old`` and the log-probs ``logp_pi`` of the
+pass that gave it, against the batch's behaviour log-probs ``logp_mu``:
+
+    w_t   = exp(logp_pi_t - logp_mu_t)
+    rho_t = min(rho_bar, w_t)            c_t = lambda min(c_bar, w_t)
+    td_t  = r_t + gamma nd_t v[t+1] - v[t]
+    A_t   = td_t + gamma nd_t lambda d_{t+1},  d_T = 0
+    d_t   = rho_t td_t + gamma nd_t c_t d_{t+1}          (d = vs - v)
+    R_t   = v[t] + d_t
+    stats as above; is_stats = [mean w, share of w > rho_bar, share of w > c_bar]
+
+A_t is r_t + gamma nd_t ((1-lambda) v[t+1] + lambda vs_{t+1}) - v[t]. With w = 1 and both bars
+>= 1 it is GAE's A_t and R_t is GAE's; at lambda = 1 R_t is V-trace's vs_t. The policy
+gradient's own importance weight is the surrogate's ratio, so ``pg_rho_bar`` plays no part.
+
 ``ppo_loss`` runs once per epoch, with ``A^ = (A - stats[0]) * stats[1]`` and
 ``ratio = exp(logp_new - logp_old)``:
 
@@ -47,7 +65,8 @@ rows t0.. of the rollout-wide logp_old / v_old / adv / ret and ``M = T/K * B``. 
 
 Device tensors run the HIP kernels (``ppo.hip``: a one-lane-per-column reverse scan with
 per-block (n, mean, M2) partials, and one vectorised elementwise pass); a missing kernel is an
-error. CPU tensors run the same maths in fp32 torch ops (``gae_torch`` / ``ppo_loss_torch`` /
+error. CPU tensors run the same maths in fp32 torch ops (``gae_torch`` / ``vtrace_adv_torch`` /
+``ppo_loss_torch`` /
 ``adv_stats_rows_torch`` / ``ppo_loss_rows_torch``: the test oracle, and what the mono
 runtime's CPU learner runs).
 """
@@ -103,6 +122,38 @@ def gae_torch(v_old, reward, done, gamma=0.99, lam=0.95, reward_clip=0.0,
     else:
         stats = torch.tensor([0.0, 1.0], dtype=v.dtype, device=v.device)
     return GaeOut(adv, adv + v[:T], stats)
+
+
+def vtrace_adv_torch(logp_pi, logp_mu, v, reward, done, gamma=0.99, lam=0.95, rho_bar=1.0,
+                     c_bar=1.0, reward_clip=0.0, norm_adv=True):
+    """``gae_torch`` with V-trace(lambda) importance weights (module docstring). Returns
+    (GaeOut, is_stats [3])."""
+    if not (rho_bar > 0 and c_bar > 0):
+        raise ValueError(f"rho_bar {rho_bar} / c_bar {c_bar}: expected > 0")
+    T, B = reward.shape
+    v = _f(v)
+    dt = v.dtype
+    w = torch.exp(_f(logp_pi).to(dt) - logp_mu.to(dt))
+    rho = w.clamp(max=rho_bar)
+    c = lam * w.clamp(max=c_bar)
+    r = reward.to(dt)
+    if reward_clip > 0:
+        r = r.clamp(-reward_clip, reward_clip)
+    disc = (~done.bool()).to(dt) * gamma
+    td = r + disc * v[1:T + 1] - v[:T]
+    acc = torch.zeros(B, dtype=dt, device=v.device)
+    adv = torch.empty_like(td)
+    d = torch.empty_like(td)
+    for t in range(T - 1, -1, -1):
+        adv[t] = td[t] + disc[t] * lam * acc
+        acc = rho[t] * td[t] + disc[t] * c[t] * acc
+        d[t] = acc
+    if norm_adv:
+        stats = torch.stack([adv.mean(), 1.0 / (adv.std(unbiased=False) + 1e-8)])
+    else:
+        stats = torch.tensor([0.0, 1.0], dtype=dt, device=v.device)
+    is_stats = torch.stack([w.mean(), (w > rho_bar).to(dt).mean(), (w > c_bar).to(dt).mean()])
+    return GaeOut(adv, v[:T] + d, stats), is_stats
 
 
 def ppo_loss_torch(logp_new, logp_old, values, v_old, adv, ret, stats, entropy=None, clip=0.1,
@@ -191,6 +242,35 @@ def gae(v_old, reward, done, gamma=0.99, lam=0.95, reward_clip=0.0, norm_adv=Tru
                                 reward_clip, int(bool(norm_adv)), adv.data_ptr(), ret.data_ptr(),
                                 partials.data_ptr(), stats.data_ptr(), N.stream_ptr()), "gae")
     return GaeOut(adv, ret, stats)
+
+
+def vtrace_adv(logp_pi, logp_mu, v, reward, done, gamma=0.99, lam=0.95, rho_bar=1.0, c_bar=1.0,
+               reward_clip=0.0, norm_adv=True, ws: VTraceWorkspace | None = None):
+    """logp_pi / logp_mu / reward / done: [T, B]; v: [T+1, B], the values of the pass that gave
+    logp_pi. Returns (GaeOut, is_stats [3] = mean w, share of w > rho_bar, share of w > c_bar);
+    the outputs live in ``ws`` under keys of their own (not ``gae``'s)."""
+    if not v.is_cuda:
+        return vtrace_adv_torch(logp_pi, logp_mu, v, reward, done, gamma, lam, rho_bar, c_bar,
+                                reward_clip, norm_adv)
+    T, B = reward.shape
+    dev = v.device
+    ws = ws or VTraceWorkspace()
+    adv = ws.get("ppo_vt_adv", (T, B), dev)
+    ret = ws.get("ppo_vt_ret", (T, B), dev)
+    partials = ws.get("ppo_vt_partials", (((B + 255) // 256) * 6,), dev)
+    stats = ws.get("ppo_vt_stats", (2,), dev)
+    is_stats = ws.get("ppo_vt_is_stats", (3,), dev)
+    c = lambda x: x.detach().float().contiguous()  # noqa: E731
+    lpi, lmu, vo, rew = c(logp_pi), c(logp_mu), c(v), c(reward)
+    dn = done.to(torch.uint8).contiguous()
+    if not (lpi.shape == lmu.shape == dn.shape == (T, B)) or vo.numel() != (T + 1) * B:
+        raise ValueError("vtrace_adv: logp_pi / logp_mu / done [T, B] and v [T+1, B] expected")
+    N.check(N.kernels().mbk_vtrace_adv(
+        lpi.data_ptr(), lmu.data_ptr(), vo.data_ptr(), rew.data_ptr(), dn.data_ptr(), T, B, gamma,
+        lam, rho_bar, c_bar, reward_clip, int(bool(norm_adv)), adv.data_ptr(), ret.data_ptr(),
+        partials.data_ptr(), stats.data_ptr(), is_stats.data_ptr(), N.stream_ptr()),
+        "vtrace_adv")
+    return GaeOut(adv, ret, stats), is_stats
 
 
 def ppo_loss(logp_new, logp_old, values, v_old, adv, ret, stats, entropy=None, clip=0.1,

@@ -29,7 +29,7 @@ from .models.factory import make_model
 from .parallel import dist as D
 from .utils.checkpoint import (load_checkpoint, load_league_shard, restore, save_checkpoint,
                                save_league_shard)
-from .utils.metrics import PPO_LOSS_COLUMNS, PPO_STEP_COLUMNS, CsvLogger
+from .utils.metrics import PPO_LOSS_COLUMNS, PPO_STEP_COLUMNS, PPO_VTRACE_COLUMNS, CsvLogger
 
 
 def scaled_lr(flags: Flags, frames_per_update: int) -> float:
@@ -66,7 +66,8 @@ def _hparams(flags: Flags, lr: float | None = None, rank: int = 0) -> LearnerHPa
                           ppo_value_clip=flags.ppo_value_clip, ppo_epochs=flags.ppo_epochs,
                           ppo_norm_adv=flags.ppo_norm_adv,
                           ppo_minibatches=flags.ppo_minibatches, ppo_shuffle=flags.ppo_shuffle,
-                          ppo_target_kl=flags.ppo_target_kl, ppo_seed=flags.seed + rank)
+                          ppo_target_kl=flags.ppo_target_kl, ppo_seed=flags.seed + rank,
+                          ppo_adv=flags.ppo_adv)
 
 
 def checkpoint_path(flags: Flags) -> str:
@@ -176,7 +177,8 @@ def resolve_runtime(flags: Flags, want_cuda: bool) -> str:
 
 def train(flags: Flags) -> dict:
     # refuses an unknown --algo, --ppo_epochs / --ppo_minibatches < 1, a --ppo_minibatches that
-    # does not divide the unroll and --ppo_target_kl < 0 before anything starts
+    # does not divide the unroll, --ppo_target_kl < 0 and an unknown --ppo_adv before anything
+    # starts
     _hparams(flags)
     want_cuda = flags.device == "cuda" or (flags.device == "auto" and torch.cuda.is_available())
     info = D.init_distributed(use_cuda=want_cuda, high_priority=flags.rccl_high_priority)
@@ -231,9 +233,13 @@ def train(flags: Flags) -> dict:
     ppo = flags.algo == "ppo"  # losses [7]: + approx_kl, clip_frac as trailing CSV columns
     # minibatches / KL early stop: + the optimiser steps each rollout took
     ppo_steps = ppo and (flags.ppo_minibatches > 1 or flags.ppo_target_kl > 0)
+    # V-trace advantages: + the shares of importance weights above --rho_bar / --c_bar, last
+    ppo_vt = ppo and flags.ppo_adv == "vtrace"
     logger = CsvLogger(flags.savedir, flags.exp_name, enabled=info.is_main, append=flags.resume,
-                       extra_loss_columns=(PPO_LOSS_COLUMNS + (PPO_STEP_COLUMNS if ppo_steps
-                                                               else []) if ppo else ()))
+                       extra_loss_columns=(PPO_LOSS_COLUMNS
+                                           + (PPO_STEP_COLUMNS if ppo_steps else [])
+                                           + (PPO_VTRACE_COLUMNS if ppo_vt else [])
+                                           if ppo else ()))
 
     league = None
     if flags.self_play and runtime != "gpu":
@@ -310,7 +316,8 @@ def train(flags: Flags) -> dict:
             logger.losses(m["update"], lv[0], lv[1], lv[2], lv[3], m["period"], m["step"],
                           m["fps"], m["wait_s"], m["learn_s"], lv[4], phase_ms=m["phase"],
                           policy_lag=m["lag"],
-                          extra=(lv[5:7] + ([m["opt_steps"]] if ppo_steps else [])) if ppo else ())
+                          extra=(lv[5:7] + ([m["opt_steps"]] if ppo_steps else [])
+                                 + (lv[7:9] if ppo_vt else [])) if ppo else ())
             last.update(update=m["update"], step=m["step"], pg_loss=lv[0], value_loss=lv[1],
                         entropy=lv[2], total_loss=lv[3], fps=m["fps"])
             log(f"update {m['update']} step {m['step']} total_loss {lv[3]:.4f} pg {lv[0]:.4f} "
@@ -405,7 +412,10 @@ def train(flags: Flags) -> dict:
                 t2 = time.perf_counter()
                 period = (t2 - t_prev) / flags.log_every  # loop period, as the reference timed it
                 t_prev = t2
-                readout.push(D.all_reduce_mean(losses.detach().clone(), info), {
+                vals = losses.detach().clone()
+                if ppo_vt:  # (learn() returns [7]: the two clip shares join the read-out here)
+                    vals = torch.cat([vals, learner.last_is_stats[1:3].to(vals.dtype)])
+                readout.push(D.all_reduce_mean(vals, info), {
                     "update": n_update, "step": step, "period": period,
                     "fps": frames_per_update / max(period, 1e-9), "wait_s": t1 - t0,
                     "learn_s": t2 - t1, "phase": learner.phases.read(), "lag": lag,

@@ -13,7 +13,8 @@
   policy_lag (learner updates between the rollout's behaviour weights and the
   update that consumed it). ``--algo ppo`` appends approx_kl and clip_frac after them
   (``extra_loss_columns``), and opt_steps after those with ``--ppo_minibatches`` > 1 or
-  ``--ppo_target_kl`` > 0; the IMPALA header and rows are unchanged.
+  ``--ppo_target_kl`` > 0, and rho_clip_frac and c_clip_frac last with ``--ppo_adv vtrace``;
+  the IMPALA header and rows are unchanged.
 
 Only rank 0 writes (DP); rows are flushed per write so a killed run keeps
 its log.
@@ -32,6 +33,8 @@ LOSS_HEADER = ["update", "pg_loss", "value_loss", "entropy_loss", "total_loss", 
 PPO_LOSS_COLUMNS = ["approx_kl", "clip_frac"]
 # --ppo_minibatches > 1 or --ppo_target_kl > 0: the optimiser steps the rollout took, after them
 PPO_STEP_COLUMNS = ["opt_steps"]
+# --ppo_adv vtrace: the shares of the rollout's importance weights above --rho_bar / --c_bar, last
+PPO_VTRACE_COLUMNS = ["rho_clip_frac", "c_clip_frac"]
 
 
 class PhaseTimer:

@@ -45,6 +45,9 @@ def main():
                     help="--algo ppo: optimiser steps per epoch, each on T / K rows of the batch")
     ap.add_argument("--ppo_target_kl", type=float, default=0.0,
                     help="--algo ppo: > 0 reads each step's approx_kl on the host (early stop)")
+    ap.add_argument("--ppo_adv", default="gae",
+                    help="--algo ppo: gae | vtrace (the V-trace(lambda) scan; K > 1: the pre-pass "
+                         "scores the actions too)")
     a = ap.parse_args()
     import torch
 
@@ -65,7 +68,7 @@ def main():
     learner = Learner(make_model(flags, dev),
                       LearnerHParams(algo=a.algo, ppo_epochs=a.ppo_epochs,
                                      ppo_minibatches=a.ppo_minibatches,
-                                     ppo_target_kl=a.ppo_target_kl), dev)
+                                     ppo_target_kl=a.ppo_target_kl, ppo_adv=a.ppo_adv), dev)
     S, T, B = a.size * a.size, a.T, a.batch
     g = torch.Generator(device=dev).manual_seed(1)
     # sparse legal-action masks with --active of the cells live, like the engine's rollouts
