@@ -68,6 +68,10 @@ _SIGS = {
     "mbk_vtrace": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                    c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p,
                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "mbk_vtrace_upgo": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                        c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_float,
+                        c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                        c_void_p, c_void_p, c_void_p],
     "mbk_gae": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_float, c_int,
                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "mbk_vtrace_adv": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,

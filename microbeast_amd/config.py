@@ -67,6 +67,11 @@ class Flags:
     ppo_adv: str = "gae"          # ppo: gae | vtrace: advantages and value targets from a
                                   # V-trace(lambda) scan clipped by --rho_bar / --c_bar, for
                                   # rollouts acted by lagged weights (GAE when on-policy)
+    vtrace_lambda: float = 1.0    # impala: V-trace(lambda) value targets, the trace cut by
+                                  # lambda * min(c_bar, w); 1 = plain V-trace, in [0, 1]
+    upgo_cost: float = 0.0        # impala: weight of the UPGO policy term (the return follows the
+                                  # rollout while it does at least as well as V); 0 = off
+    upgo_rho_bar: float = 1.0     # impala: importance-weight bar of the UPGO term, > 0
     # --- environment
     env: str = "synthetic"        # synthetic | microrts (gym-microrts adapter, if installed)
     opponents: str = "coac,coac,coac,random_biased,light_rush,worker_rush"

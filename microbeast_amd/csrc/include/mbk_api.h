@@ -157,6 +157,26 @@ int mbk_ppo_loss_rows(const float* logp_new, const float* logp_old, const float*
                       float* g_value, float* partials, float* losses, float* epoch_mean,
                       hipStream_t stream);
 
+// ---- IMPALA objective with V-trace(lambda) targets and the UPGO term (vtrace.hip) -----------
+// mbk_vtrace's arrays (time-major fp32 [T, B]; values / g_value [T+1, B], row T the bootstrap,
+// its gradient zeroed; entropy may be null) with the trace cut by lambda * min(c_bar, w) and a
+// second policy-gradient term on the upgoing return
+//   G_t = r_t + g_t (q_{t+1} >= V_{t+1} ? G_{t+1} : V_{t+1}),  q_t = r_t + g_t V_{t+1},
+//   G_{T-1} = q_{T-1},  upgo_adv_t = min(upgo_rho_bar, w_t) (G_t - V_t),
+//   g_logp_t = -(adv_t + upgo_cost upgo_adv_t) / (T B).
+// vs_out, adv_out, upgo_out (G) [T, B] may each be null. losses[6] = pg (V-trace term alone),
+// value, entropy, total (= pg + upgo_cost upgo + value - entropy_cost entropy), mean rho, upgo
+// (unweighted). partials: 5 * ceil(B / 256) floats. Ordered, no atomics. Refused with
+// hipErrorInvalidValue, nothing launched: T < 1, B < 1, lambda outside [0, 1], upgo_cost < 0,
+// upgo_rho_bar <= 0.
+int mbk_vtrace_upgo(const float* logp_new, const float* logp_old, const float* values,
+                    const float* reward, const uint8_t* done, const float* entropy, int T, int B,
+                    float gamma, float lambda, float rho_bar, float c_bar, float pg_rho_bar,
+                    float upgo_rho_bar, float baseline_cost, float entropy_cost, float upgo_cost,
+                    float reward_clip, float* vs_out, float* adv_out, float* upgo_out,
+                    float* g_logp, float* g_value, float* partials, float* losses,
+                    hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

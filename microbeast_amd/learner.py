@@ -26,7 +26,7 @@ import torch
 from .ops.copy import full, multi_copy
 from .ops.optim import FlatAdam, FlatParams
 from .ops.ppo import adv_stats_rows, gae, ppo_loss, ppo_loss_rows, vtrace_adv
-from .ops.vtrace import VTraceWorkspace, vtrace
+from .ops.vtrace import VTraceWorkspace, vtrace, vtrace_upgo
 from .parallel.dist import DistInfo, GradAllReducer, broadcast_flat, host_max
 from .utils.metrics import PhaseTimer
 
@@ -57,10 +57,23 @@ class LearnerHParams:
     ppo_target_kl: float = 0.0     # ppo: > 0 ends the rollout's steps after one exceeds it
     ppo_seed: int = 0              # ppo: seeds the block orders (with n_updates and the epoch)
     ppo_adv: str = "gae"           # ppo: gae | vtrace (rho_bar / c_bar-clipped, ops/ppo.py)
+    vtrace_lambda: float = 1.0     # impala: V-trace(lambda), the trace cut by lambda min(c_bar, w)
+    upgo_cost: float = 0.0         # impala: weight of the UPGO policy term (0: off)
+    upgo_rho_bar: float = 1.0      # impala: importance-weight bar of the UPGO term
 
     def __post_init__(self):
         if self.algo not in ("impala", "ppo"):
             raise ValueError(f"--algo {self.algo!r}: expected impala | ppo")
+        if not 0.0 <= self.vtrace_lambda <= 1.0:
+            raise ValueError(f"--vtrace_lambda {self.vtrace_lambda}: expected 0 <= lambda <= 1")
+        if not self.upgo_cost >= 0:
+            raise ValueError(f"--upgo_cost {self.upgo_cost}: expected >= 0 (0 = off)")
+        if not self.upgo_rho_bar > 0:
+            raise ValueError(f"--upgo_rho_bar {self.upgo_rho_bar}: expected > 0")
+        if self.algo == "ppo" and (self.upgo_cost > 0 or self.vtrace_lambda != 1.0):
+            raise ValueError(f"--algo ppo: --upgo_cost {self.upgo_cost} / --vtrace_lambda "
+                             f"{self.vtrace_lambda} act on the IMPALA objective only (PPO's trace "
+                             "is cut by --gae_lambda)")
         if self.ppo_adv not in ("gae", "vtrace"):
             raise ValueError(f"--ppo_adv {self.ppo_adv!r}: expected gae | vtrace")
         if self.ppo_adv == "vtrace" and not (self.rho_bar > 0 and self.c_bar > 0):
@@ -116,7 +129,8 @@ class Learner:
         """batch keys (time-major): obs [T+1,B,...], mask [T+1,B,S,3] int32,
         action [T+1,B,S,7] uint8, logp [T+1,B], reward [T+1,B], done [T+1,B].
         Returns the device tensor [5] = pg, value, entropy, total, mean rho (``algo="ppo"``:
-        [7], see ``_learn_ppo``)."""
+        [7], see ``_learn_ppo``; ``vtrace_lambda`` < 1 or ``upgo_cost`` > 0: [6], + the
+        unweighted UPGO loss, from ``ops.vtrace.vtrace_upgo`` in ``vtrace``'s place)."""
         if self.hp.algo == "ppo":
             return self._learn_ppo(batch, sync_timing)
         t0 = time.perf_counter()
@@ -136,11 +150,20 @@ class Learner:
             # the acting step's active-cell bitmap: the head compaction skips the mask pass
             kw["abits"] = ab[:T].reshape(T * B, ab.shape[-1])
         logp, ent, value = self.model.evaluate(flat_obs, m, a, n_score=T * B, **kw)
-        vt = vtrace(logp.view(T, B), batch["logp"][:T], value.view(T1, B), batch["reward"][:T],
-                    batch["done"][:T], ent.view(T, B), gamma=self.hp.gamma, rho_bar=self.hp.rho_bar,
-                    c_bar=self.hp.c_bar, pg_rho_bar=self.hp.pg_rho_bar,
-                    baseline_cost=self.hp.baseline_cost, entropy_cost=self.hp.entropy_cost,
-                    reward_clip=self.hp.reward_clip, ws=self.ws)
+        if self.hp.vtrace_lambda == 1.0 and self.hp.upgo_cost == 0.0:
+            vt = vtrace(logp.view(T, B), batch["logp"][:T], value.view(T1, B), batch["reward"][:T],
+                        batch["done"][:T], ent.view(T, B), gamma=self.hp.gamma, rho_bar=self.hp.rho_bar,
+                        c_bar=self.hp.c_bar, pg_rho_bar=self.hp.pg_rho_bar,
+                        baseline_cost=self.hp.baseline_cost, entropy_cost=self.hp.entropy_cost,
+                        reward_clip=self.hp.reward_clip, ws=self.ws)
+        else:  # V-trace(lambda) targets and / or the UPGO term: losses [6]
+            vt = vtrace_upgo(logp.view(T, B), batch["logp"][:T], value.view(T1, B),
+                             batch["reward"][:T], batch["done"][:T], ent.view(T, B),
+                             gamma=self.hp.gamma, rho_bar=self.hp.rho_bar, c_bar=self.hp.c_bar,
+                             pg_rho_bar=self.hp.pg_rho_bar, baseline_cost=self.hp.baseline_cost,
+                             entropy_cost=self.hp.entropy_cost, reward_clip=self.hp.reward_clip,
+                             lam=self.hp.vtrace_lambda, upgo_cost=self.hp.upgo_cost,
+                             upgo_rho_bar=self.hp.upgo_rho_bar, ws=self.ws)
         self.phases.mark("fwd")
         if sync_timing and logp.is_cuda:
             torch.cuda.synchronize()

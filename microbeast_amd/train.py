@@ -29,7 +29,8 @@ from .models.factory import make_model
 from .parallel import dist as D
 from .utils.checkpoint import (load_checkpoint, load_league_shard, restore, save_checkpoint,
                                save_league_shard)
-from .utils.metrics import PPO_LOSS_COLUMNS, PPO_STEP_COLUMNS, PPO_VTRACE_COLUMNS, CsvLogger
+from .utils.metrics import (PPO_LOSS_COLUMNS, PPO_STEP_COLUMNS, PPO_VTRACE_COLUMNS,
+                            UPGO_LOSS_COLUMNS, CsvLogger)
 
 
 def scaled_lr(flags: Flags, frames_per_update: int) -> float:
@@ -67,7 +68,8 @@ def _hparams(flags: Flags, lr: float | None = None, rank: int = 0) -> LearnerHPa
                           ppo_norm_adv=flags.ppo_norm_adv,
                           ppo_minibatches=flags.ppo_minibatches, ppo_shuffle=flags.ppo_shuffle,
                           ppo_target_kl=flags.ppo_target_kl, ppo_seed=flags.seed + rank,
-                          ppo_adv=flags.ppo_adv)
+                          ppo_adv=flags.ppo_adv, vtrace_lambda=flags.vtrace_lambda,
+                          upgo_cost=flags.upgo_cost, upgo_rho_bar=flags.upgo_rho_bar)
 
 
 def checkpoint_path(flags: Flags) -> str:
@@ -177,8 +179,8 @@ def resolve_runtime(flags: Flags, want_cuda: bool) -> str:
 
 def train(flags: Flags) -> dict:
     # refuses an unknown --algo, --ppo_epochs / --ppo_minibatches < 1, a --ppo_minibatches that
-    # does not divide the unroll, --ppo_target_kl < 0 and an unknown --ppo_adv before anything
-    # starts
+    # does not divide the unroll, --ppo_target_kl < 0, an unknown --ppo_adv, and --vtrace_lambda /
+    # --upgo_cost / --upgo_rho_bar out of range or under --algo ppo before anything starts
     _hparams(flags)
     want_cuda = flags.device == "cuda" or (flags.device == "auto" and torch.cuda.is_available())
     info = D.init_distributed(use_cuda=want_cuda, high_priority=flags.rccl_high_priority)
@@ -235,11 +237,13 @@ def train(flags: Flags) -> dict:
     ppo_steps = ppo and (flags.ppo_minibatches > 1 or flags.ppo_target_kl > 0)
     # V-trace advantages: + the shares of importance weights above --rho_bar / --c_bar, last
     ppo_vt = ppo and flags.ppo_adv == "vtrace"
+    # --upgo_cost > 0 (IMPALA): losses [6], + the unweighted UPGO loss as one trailing column
+    upgo = not ppo and flags.upgo_cost > 0
     logger = CsvLogger(flags.savedir, flags.exp_name, enabled=info.is_main, append=flags.resume,
                        extra_loss_columns=(PPO_LOSS_COLUMNS
                                            + (PPO_STEP_COLUMNS if ppo_steps else [])
                                            + (PPO_VTRACE_COLUMNS if ppo_vt else [])
-                                           if ppo else ()))
+                                           if ppo else UPGO_LOSS_COLUMNS if upgo else ()))
 
     league = None
     if flags.self_play and runtime != "gpu":
@@ -317,11 +321,13 @@ def train(flags: Flags) -> dict:
                           m["fps"], m["wait_s"], m["learn_s"], lv[4], phase_ms=m["phase"],
                           policy_lag=m["lag"],
                           extra=(lv[5:7] + ([m["opt_steps"]] if ppo_steps else [])
-                                 + (lv[7:9] if ppo_vt else [])) if ppo else ())
+                                 + (lv[7:9] if ppo_vt else [])) if ppo
+                          else lv[5:6] if upgo else ())
             last.update(update=m["update"], step=m["step"], pg_loss=lv[0], value_loss=lv[1],
                         entropy=lv[2], total_loss=lv[3], fps=m["fps"])
             log(f"update {m['update']} step {m['step']} total_loss {lv[3]:.4f} pg {lv[0]:.4f} "
-                f"v {lv[1]:.4f} ent {lv[2]:.3f} fps {m['fps']:,.0f} lag {m['lag']}"
+                f"v {lv[1]:.4f} ent {lv[2]:.3f}" + (f" upgo {lv[5]:.4f}" if upgo else "")
+                + f" fps {m['fps']:,.0f} lag {m['lag']}"
                 + (f" league {m['league']}" if m.get("league") else ""))
 
     held = None  # gpu runtime: a batch kept over a round in which a DP peer restarted

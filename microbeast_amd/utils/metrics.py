@@ -14,7 +14,9 @@
   update that consumed it). ``--algo ppo`` appends approx_kl and clip_frac after them
   (``extra_loss_columns``), and opt_steps after those with ``--ppo_minibatches`` > 1 or
   ``--ppo_target_kl`` > 0, and rho_clip_frac and c_clip_frac last with ``--ppo_adv vtrace``;
-  the IMPALA header and rows are unchanged.
+  ``--upgo_cost`` > 0 (IMPALA) appends upgo_loss, the unweighted UPGO term (pg_loss stays the
+  V-trace term alone; total_loss holds their weighted sum); with ``--vtrace_lambda`` alone, and
+  by default, the IMPALA header and rows are unchanged.
 
 Only rank 0 writes (DP); rows are flushed per write so a killed run keeps
 its log.
@@ -35,6 +37,8 @@ PPO_LOSS_COLUMNS = ["approx_kl", "clip_frac"]
 PPO_STEP_COLUMNS = ["opt_steps"]
 # --ppo_adv vtrace: the shares of the rollout's importance weights above --rho_bar / --c_bar, last
 PPO_VTRACE_COLUMNS = ["rho_clip_frac", "c_clip_frac"]
+# --upgo_cost > 0 (IMPALA): the unweighted UPGO loss -mean(logp * upgo_adv), after policy_lag
+UPGO_LOSS_COLUMNS = ["upgo_loss"]
 
 
 class PhaseTimer:

@@ -48,6 +48,12 @@ def main():
     ap.add_argument("--ppo_adv", default="gae",
                     help="--algo ppo: gae | vtrace (the V-trace(lambda) scan; K > 1: the pre-pass "
                          "scores the actions too)")
+    ap.add_argument("--vtrace_lambda", type=float, default=1.0,
+                    help="--algo impala: V-trace(lambda); off 1 the objective is mbk_vtrace_upgo")
+    ap.add_argument("--upgo_cost", type=float, default=0.0,
+                    help="--algo impala: weight of the UPGO term; > 0: mbk_vtrace_upgo")
+    ap.add_argument("--upgo_rho_bar", type=float, default=1.0,
+                    help="--algo impala: importance-weight bar of the UPGO term")
     a = ap.parse_args()
     import torch
 
@@ -68,7 +74,9 @@ def main():
     learner = Learner(make_model(flags, dev),
                       LearnerHParams(algo=a.algo, ppo_epochs=a.ppo_epochs,
                                      ppo_minibatches=a.ppo_minibatches,
-                                     ppo_target_kl=a.ppo_target_kl, ppo_adv=a.ppo_adv), dev)
+                                     ppo_target_kl=a.ppo_target_kl, ppo_adv=a.ppo_adv,
+                                     vtrace_lambda=a.vtrace_lambda, upgo_cost=a.upgo_cost,
+                                     upgo_rho_bar=a.upgo_rho_bar), dev)
     S, T, B = a.size * a.size, a.T, a.batch
     g = torch.Generator(device=dev).manual_seed(1)
     # sparse legal-action masks with --active of the cells live, like the engine's rollouts
