@@ -52,7 +52,9 @@ def cell_head_torch(logits: torch.Tensor, mask: torch.Tensor, action: torch.Tens
     Returns (action [N,S,7] uint8, logp [N], entropy [N]) — differentiable in logits.
     """
     n = logits.shape[0]
-    z = logits.float().view(n, -1, CELL)
+    # (float64 logits stay float64: the tests' high-precision form. There a fully masked segment
+    # scores -log n instead of fp32's rounded 0; the callers that use it account for that.)
+    z = (logits if logits.dtype == torch.float64 else logits.float()).view(n, -1, CELL)
     if mask.dtype != torch.bool:
         mask = unpack_mask(mask)
     mask = mask.view(n, -1, CELL)
