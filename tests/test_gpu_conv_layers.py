@@ -21,56 +21,11 @@ import pytest
 import torch
 
 import conv_cases as cc
+from guarded import GuardedTorch as _GuardedTorch, filled
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 4096
 INVALID = 1  # hipErrorInvalidValue
-
-
-class _GuardedTorch:
-    """Stands in for ``torch`` inside ops/encoder.py: every torch.empty there, and every output
-    the tests allocate, is the middle of a larger buffer of 0xFF bytes."""
-
-    def __init__(self):
-        self.bufs = []
-
-    def __getattr__(self, name):
-        return getattr(torch, name)
-
-    def empty(self, *shape, dtype=None, device=None):
-        if len(shape) == 1 and not isinstance(shape[0], int):
-            shape = tuple(shape[0])
-        nbytes = torch.empty((), dtype=dtype).element_size()
-        for s in shape:
-            nbytes *= int(s)
-        raw = torch.full((2 * GUARD + (nbytes + 255) // 256 * 256,), 0xFF, dtype=torch.uint8,
-                         device=device)
-        t = raw[GUARD:GUARD + nbytes].view(dtype).view(*shape)
-        # (fp32: the encoder's partial-row workspace, sized for the largest batch, is not an
-        # output; the fp32 outputs dW / db are checked by the caller)
-        self.bufs.append((raw, nbytes, t, dtype != torch.float32))
-        return t
-
-    def empty_like(self, t):
-        return self.empty(*t.shape, dtype=t.dtype, device=t.device)
-
-    def check(self):
-        torch.cuda.synchronize()
-        for raw, nbytes, t, interior in self.bufs:
-            assert bool((raw[:GUARD] == 0xFF).all()) and bool((raw[GUARD + nbytes:] == 0xFF).all()), \
-                f"write outside an output of shape {tuple(t.shape)}"
-            if interior:
-                filled(t)
-        self.bufs = []
-
-
-def filled(t):
-    """No 0xFF fill pattern is left inside output t."""
-    if t.dtype == torch.uint8:
-        assert bool((t <= 8).all()), "window byte not written"
-    else:
-        assert not bool(torch.isnan(t).any()), "output element not written"
 
 
 @pytest.fixture
