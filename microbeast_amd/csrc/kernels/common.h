@@ -305,6 +305,28 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// A 256-lane block's K sums -> its partial row out[K]: wave_sum each, LDS, thread k < K adds
+// the waves in order 0..3 from 0. The first pass of every two-pass ordered reduction of
+// vtrace.hip / ppo.hip (no float atomics: the same bits in every run). All lanes call it.
+template <int K>
+__device__ __forceinline__ void block_sums(const float (&s)[K], float* __restrict__ out) {
+  __shared__ float red[4][K];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  float w[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) w[k] = wave_sum(s[k]);  // (all K first: the shuffles interleave)
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) red[wave][k] = w[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < K) {
+    float t = 0.f;
+    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += red[i][threadIdx.x];
+    out[threadIdx.x] = t;
+  }
+}
+
 // ------------------------------------------------------------------ pooled epilogue
 // max_pool2d(3, 2, 1) of the workgroup's conv outputs staged in LDS (otile [(im*H+y)*W+x]
 // [OSTR] bf16) -> pooled y + per-channel argmax (ky*3+kx, first maximum in scan order as

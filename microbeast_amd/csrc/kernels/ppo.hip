@@ -38,6 +38,11 @@
 // Every reduction is two-pass and ordered (per-block partials, one finalize wave): no float
 // atomics, bit-reproducible between runs. The advantage statistics merge per-block
 // (n, mean, M2) triples (Chan et al.), not a global sum of squares.
+//
+// Each step exists once: push / block_merge / write_stats below serve the three kernels that
+// keep moments and their finalizes, block_sums<K> (common.h) is the first pass of every plain
+// sum (shared with vtrace.hip), ppo_finalize_kernel serves both loss launchers (epoch_mean
+// null: none kept), and launch_ppo_loss holds the vector / scalar choice and both launches.
 #include "../include/mbk_api.h"
 #include "common.h"
 
@@ -67,6 +72,35 @@ __device__ __forceinline__ Moments wave_merge(Moments m) {
   }
   return m;
 }
+// Welford update of a lane's own running value
+__device__ __forceinline__ void push(Moments& m, float x) {
+  m.n += 1.f;
+  const float d = x - m.mean;
+  m.mean += d / m.n;
+  m.m2 += d * (x - m.mean);
+}
+// A 256-lane block's merge -> its partial triple out[3]: wave_merge, LDS, thread 0 merges the
+// waves in order. All lanes call it.
+__device__ __forceinline__ void block_merge(Moments mo, float* __restrict__ out) {
+  __shared__ Moments red[4];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  mo = wave_merge(mo);
+  if (lane == 0) red[wave] = mo;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    Moments s = red[0];
+    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) s = merge(s, red[w]);
+    out[0] = s.n;
+    out[1] = s.mean;
+    out[2] = s.m2;
+  }
+}
+// stats[0..1] = mean, 1 / (std + 1e-8) (population std); (0, 1) with normalisation off
+__device__ __forceinline__ void write_stats(Moments s, int norm, float* __restrict__ stats) {
+  const float sd = sqrtf(fmaxf(s.m2, 0.f) / fmaxf(s.n, 1.f));
+  stats[0] = norm ? s.mean : 0.f;
+  stats[1] = norm ? 1.f / (sd + 1e-8f) : 1.f;
+}
 
 __global__ __launch_bounds__(256) void gae_kernel(
     const float* __restrict__ v_old, const float* __restrict__ reward,
@@ -88,29 +122,13 @@ __global__ __launch_bounds__(256) void gae_kernel(
       acc = delta + disc * lambda * acc;
       adv_out[i] = acc;
       ret_out[i] = acc + v;
-      // Welford update of the lane's own column
-      mo.n += 1.f;
-      const float d = acc - mo.mean;
-      mo.mean += d / mo.n;
-      mo.m2 += d * (acc - mo.mean);
+      push(mo, acc);
       v_next = v;
     }
   }
-  __shared__ Moments red[4];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  mo = wave_merge(mo);
-  if (lane == 0) red[wave] = mo;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    Moments s = red[0];
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) s = merge(s, red[w]);
-    partials[blockIdx.x * 3 + 0] = s.n;
-    partials[blockIdx.x * 3 + 1] = s.mean;
-    partials[blockIdx.x * 3 + 2] = s.m2;
-  }
+  block_merge(mo, partials + blockIdx.x * 3);
 }
 
-// stats[0..1] = mean, 1 / (std + 1e-8); (0, 1) with normalisation off
 __global__ __launch_bounds__(64) void gae_finalize_kernel(const float* __restrict__ partials,
                                                           int nblocks, int norm,
                                                           float* __restrict__ stats) {
@@ -119,11 +137,7 @@ __global__ __launch_bounds__(64) void gae_finalize_kernel(const float* __restric
   for (int i = lane; i < nblocks; i += 64)
     s = merge(s, Moments{partials[i * 3], partials[i * 3 + 1], partials[i * 3 + 2]});
   s = wave_merge(s);
-  if (lane == 0) {
-    const float sd = sqrtf(fmaxf(s.m2, 0.f) / fmaxf(s.n, 1.f));
-    stats[0] = norm ? s.mean : 0.f;
-    stats[1] = norm ? 1.f / (sd + 1e-8f) : 1.f;
-  }
+  if (lane == 0) write_stats(s, norm, stats);
 }
 
 // V-trace(lambda) advantages for lagged rollouts: gae_kernel with the importance weights
@@ -157,43 +171,16 @@ __global__ __launch_bounds__(256) void vtrace_adv_kernel(
       acc = fminf(rho_bar, w) * delta + disc * (lambda * fminf(c_bar, w)) * acc;
       adv_out[i] = a;
       ret_out[i] = acc + v;
-      mo.n += 1.f;
-      const float d = a - mo.mean;
-      mo.mean += d / mo.n;
-      mo.m2 += d * (a - mo.mean);
+      push(mo, a);
       is[0] += w;
       is[1] += w > rho_bar ? 1.f : 0.f;
       is[2] += w > c_bar ? 1.f : 0.f;
       v_next = v;
     }
   }
-  __shared__ Moments red[4];
-  __shared__ float red_is[4][3];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  mo = wave_merge(mo);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) is[k] = wave_sum(is[k]);
-  if (lane == 0) {
-    red[wave] = mo;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) red_is[wave][k] = is[k];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    Moments s = red[0];
-    float t[3] = {red_is[0][0], red_is[0][1], red_is[0][2]};
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) {
-      s = merge(s, red[w]);
-      for (int k = 0; k < 3; ++k) t[k] += red_is[w][k];
-    }
-    float* out = partials + (size_t)blockIdx.x * kVtParts;
-    out[0] = s.n;
-    out[1] = s.mean;
-    out[2] = s.m2;
-    out[3] = t[0];
-    out[4] = t[1];
-    out[5] = t[2];
-  }
+  float* out = partials + (size_t)blockIdx.x * kVtParts;
+  block_merge(mo, out);
+  block_sums<3>(is, out + 3);
 }
 
 // gae_finalize_kernel's stats, and is_stats[0..2] = mean w, share of w > rho_bar, share of
@@ -212,9 +199,7 @@ __global__ __launch_bounds__(64) void vtrace_adv_finalize_kernel(
   s = wave_merge(s);
   for (int k = 0; k < 3; ++k) t[k] = wave_sum(t[k]);
   if (lane == 0) {
-    const float sd = sqrtf(fmaxf(s.m2, 0.f) / fmaxf(s.n, 1.f));
-    stats[0] = norm ? s.mean : 0.f;
-    stats[1] = norm ? 1.f / (sd + 1e-8f) : 1.f;
+    write_stats(s, norm, stats);
     for (int k = 0; k < 3; ++k) is_stats[k] = t[k] * invM;
   }
 }
@@ -307,95 +292,13 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(
       g_value[i] = 0.f;
     }
   }
-  __shared__ float red[4][kSums];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int k = 0; k < kSums; ++k) {
-    const float w = wave_sum(s[k]);
-    if (lane == 0) red[wave][k] = w;
-  }
-  __syncthreads();
-  if (threadIdx.x < kSums) {
-    float t = 0.f;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += red[w][threadIdx.x];
-    partials[(size_t)blockIdx.x * kSums + threadIdx.x] = t;
-  }
+  block_sums<kSums>(s, partials + (size_t)blockIdx.x * kSums);
 }
 
-// losses[0..6] = pg, value, entropy, total, mean ratio, approx_kl, clip_frac
-__global__ __launch_bounds__(64) void ppo_finalize_kernel(const float* __restrict__ partials,
-                                                          int nblocks, size_t M,
-                                                          float baseline_cost, float entropy_cost,
-                                                          float* __restrict__ losses) {
-  const int lane = threadIdx.x;
-  float s[kSums] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int i = lane; i < nblocks; i += 64)
-    for (int k = 0; k < kSums; ++k) s[k] += partials[(size_t)i * kSums + k];
-  for (int k = 0; k < kSums; ++k) s[k] = wave_sum(s[k]);
-  if (lane == 0) {
-    const float invM = 1.f / (float)M;
-    const float pg = -s[0] * invM, vl = baseline_cost * s[1] * invM, ent = s[2] * invM;
-    losses[0] = pg;
-    losses[1] = vl;
-    losses[2] = ent;
-    losses[3] = pg + vl - entropy_cost * ent;
-    losses[4] = s[3] * invM;
-    losses[5] = s[4] * invM;
-    losses[6] = s[5] * invM;
-  }
-}
-
-// ---- row-block minibatches: per-block advantage statistics and the block loss's finalize ----
-
-// Block k = rows [k Tm, (k+1) Tm) of adv: n = Tm*B contiguous elements. gridDim = (nb, K);
-// thread j of the nb*256 of a block takes elements j, j + nb*256, ... (a fixed assignment, so
-// the moments do not depend on the run). partials [K][nb][3].
-__global__ __launch_bounds__(256) void adv_stats_rows_kernel(const float* __restrict__ adv,
-                                                             size_t n,
-                                                             float* __restrict__ partials) {
-  const float* a = adv + (size_t)blockIdx.y * n;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  Moments mo = {0.f, 0.f, 0.f};
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float x = a[i];
-    mo.n += 1.f;
-    const float d = x - mo.mean;
-    mo.mean += d / mo.n;
-    mo.m2 += d * (x - mo.mean);
-  }
-  __shared__ Moments red[4];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  mo = wave_merge(mo);
-  if (lane == 0) red[wave] = mo;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    Moments s = red[0];
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) s = merge(s, red[w]);
-    float* out = partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 3;
-    out[0] = s.n;
-    out[1] = s.mean;
-    out[2] = s.m2;
-  }
-}
-
-// one wave per block k: stats[k] = mean, 1 / (std + 1e-8); (0, 1) with normalisation off
-__global__ __launch_bounds__(64) void adv_stats_rows_finalize_kernel(
-    const float* __restrict__ partials, int nb, int norm, float* __restrict__ stats) {
-  const int lane = threadIdx.x;
-  const float* p = partials + (size_t)blockIdx.x * nb * 3;
-  Moments s = {0.f, 0.f, 0.f};
-  for (int i = lane; i < nb; i += 64) s = merge(s, Moments{p[i * 3], p[i * 3 + 1], p[i * 3 + 2]});
-  s = wave_merge(s);
-  if (lane == 0) {
-    const float sd = sqrtf(fmaxf(s.m2, 0.f) / fmaxf(s.n, 1.f));
-    stats[blockIdx.x * 2 + 0] = norm ? s.mean : 0.f;
-    stats[blockIdx.x * 2 + 1] = norm ? 1.f / (sd + 1e-8f) : 1.f;
-  }
-}
-
-// ppo_finalize_kernel for one step of an epoch: losses[7] of the step, and the ordered running
-// mean of the epoch's steps so far (step 0 restarts it)
-__global__ __launch_bounds__(64) void ppo_rows_finalize_kernel(
+// losses[0..6] = pg, value, entropy, total, mean ratio, approx_kl, clip_frac. epoch_mean (null:
+// none kept): the ordered running mean of the per-step losses of a row-block epoch so far
+// (step 0 restarts it)
+__global__ __launch_bounds__(64) void ppo_finalize_kernel(
     const float* __restrict__ partials, int nblocks, size_t M, float baseline_cost,
     float entropy_cost, int step, float* __restrict__ losses, float* __restrict__ epoch_mean) {
   const int lane = threadIdx.x;
@@ -412,12 +315,63 @@ __global__ __launch_bounds__(64) void ppo_rows_finalize_kernel(
 #pragma unroll
     for (int k = 0; k < 7; ++k) {
       losses[k] = l[k];
-      epoch_mean[k] = step == 0 ? l[k] : epoch_mean[k] + (l[k] - epoch_mean[k]) * inv;
+      if (epoch_mean)
+        epoch_mean[k] = step == 0 ? l[k] : epoch_mean[k] + (l[k] - epoch_mean[k]) * inv;
     }
   }
 }
 
+// ---- row-block minibatches: per-block advantage statistics ----
+
+// Block k = rows [k Tm, (k+1) Tm) of adv: n = Tm*B contiguous elements. gridDim = (nb, K);
+// thread j of the nb*256 of a block takes elements j, j + nb*256, ... (a fixed assignment, so
+// the moments do not depend on the run). partials [K][nb][3].
+__global__ __launch_bounds__(256) void adv_stats_rows_kernel(const float* __restrict__ adv,
+                                                             size_t n,
+                                                             float* __restrict__ partials) {
+  const float* a = adv + (size_t)blockIdx.y * n;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  Moments mo = {0.f, 0.f, 0.f};
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+    push(mo, a[i]);
+  block_merge(mo, partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 3);
+}
+
+// one wave per block k: stats[k] = mean, 1 / (std + 1e-8); (0, 1) with normalisation off
+__global__ __launch_bounds__(64) void adv_stats_rows_finalize_kernel(
+    const float* __restrict__ partials, int nb, int norm, float* __restrict__ stats) {
+  const int lane = threadIdx.x;
+  const float* p = partials + (size_t)blockIdx.x * nb * 3;
+  Moments s = {0.f, 0.f, 0.f};
+  for (int i = lane; i < nb; i += 64) s = merge(s, Moments{p[i * 3], p[i * 3 + 1], p[i * 3 + 2]});
+  s = wave_merge(s);
+  if (lane == 0) write_stats(s, norm, stats + blockIdx.x * 2);
+}
+
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+// ppo_loss_kernel on M elements (items M.. up to MB: g_value's rows to zero) and its finalize;
+// the vector kernel where B % 4 == 0 and every array is 16-byte aligned. epoch_mean may be null.
+int launch_ppo_loss(const float* logp_new, const float* logp_old, const float* values,
+                    const float* v_old, const float* adv, const float* ret, const float* entropy,
+                    const float* stats, size_t M, size_t MB, int B, float clip_lo, float clip_hi,
+                    float clip, float value_clip, float baseline_cost, float entropy_cost,
+                    int step, float* g_logp, float* g_value, float* partials, float* losses,
+                    float* epoch_mean, hipStream_t stream) {
+  const bool vec = B % 4 == 0 && aligned16(logp_new) && aligned16(logp_old) &&
+                   aligned16(values) && aligned16(v_old) && aligned16(adv) && aligned16(ret) &&
+                   (!entropy || aligned16(entropy)) && aligned16(g_logp) && aligned16(g_value);
+  const size_t items = vec ? MB / 4 : MB;
+  const size_t nb = (items + 255) / 256;
+  if (nb > 0x7fffffffull) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(vec ? ppo_loss_kernel<4> : ppo_loss_kernel<1>, dim3((unsigned)nb), dim3(256),
+                     0, stream, logp_new, logp_old, values, v_old, adv, ret, entropy, stats, M,
+                     MB, clip_lo, clip_hi, clip, value_clip, baseline_cost, g_logp, g_value,
+                     partials);
+  hipLaunchKernelGGL(ppo_finalize_kernel, dim3(1), dim3(64), 0, stream, partials, (int)nb, M,
+                     baseline_cost, entropy_cost, step, losses, epoch_mean);
+  return (int)hipGetLastError();
+}
 
 // blocks of 256 lanes per row block in adv_stats_rows_kernel
 inline int stats_rows_blocks(size_t n) {
@@ -449,28 +403,11 @@ extern "C" int mbk_ppo_loss_rows(const float* logp_new, const float* logp_old,
                                  float* losses, float* epoch_mean, hipStream_t stream) {
   if (t0 < 0 || Tm < 1 || B < 1 || step < 0) return (int)hipErrorInvalidValue;
   const size_t M = (size_t)Tm * B, off = (size_t)t0 * B;
-  logp_old += off;
-  v_old += off;
-  adv += off;
-  ret += off;
-  const bool vec = B % 4 == 0 && aligned16(logp_new) && aligned16(logp_old) &&
-                   aligned16(values) && aligned16(v_old) && aligned16(adv) && aligned16(ret) &&
-                   (!entropy || aligned16(entropy)) && aligned16(g_logp) && aligned16(g_value);
-  const size_t items = vec ? M / 4 : M;
-  const size_t nb = (items + 255) / 256;
-  if (nb > 0x7fffffffull) return (int)hipErrorInvalidValue;
   // (MB = M: the step's arrays have no bootstrap row to zero)
-  if (vec)
-    hipLaunchKernelGGL(ppo_loss_kernel<4>, dim3((unsigned)nb), dim3(256), 0, stream, logp_new,
-                       logp_old, values, v_old, adv, ret, entropy, stats, M, M, clip_lo, clip_hi,
-                       clip, value_clip, baseline_cost, g_logp, g_value, partials);
-  else
-    hipLaunchKernelGGL(ppo_loss_kernel<1>, dim3((unsigned)nb), dim3(256), 0, stream, logp_new,
-                       logp_old, values, v_old, adv, ret, entropy, stats, M, M, clip_lo, clip_hi,
-                       clip, value_clip, baseline_cost, g_logp, g_value, partials);
-  hipLaunchKernelGGL(ppo_rows_finalize_kernel, dim3(1), dim3(64), 0, stream, partials, (int)nb, M,
-                     baseline_cost, entropy_cost, step, losses, epoch_mean);
-  return (int)hipGetLastError();
+  return launch_ppo_loss(logp_new, logp_old + off, values, v_old + off, adv + off, ret + off,
+                         entropy, stats, M, M, B, clip_lo, clip_hi, clip, value_clip,
+                         baseline_cost, entropy_cost, step, g_logp, g_value, partials, losses,
+                         epoch_mean, stream);
 }
 
 extern "C" int mbk_gae(const float* v_old, const float* reward, const uint8_t* done, int T, int B,
@@ -510,22 +447,8 @@ extern "C" int mbk_ppo_loss(const float* logp_new, const float* logp_old, const 
                             float baseline_cost, float entropy_cost, float* g_logp,
                             float* g_value, float* partials, float* losses, hipStream_t stream) {
   if (T < 1 || B < 1) return (int)hipErrorInvalidValue;
-  const size_t M = (size_t)T * B, MB = M + (size_t)B;
-  const bool vec = B % 4 == 0 && aligned16(logp_new) && aligned16(logp_old) &&
-                   aligned16(values) && aligned16(v_old) && aligned16(adv) && aligned16(ret) &&
-                   (!entropy || aligned16(entropy)) && aligned16(g_logp) && aligned16(g_value);
-  const size_t items = vec ? MB / 4 : MB;
-  const size_t nb = (items + 255) / 256;
-  if (nb > 0x7fffffffull) return (int)hipErrorInvalidValue;
-  if (vec)
-    hipLaunchKernelGGL(ppo_loss_kernel<4>, dim3((unsigned)nb), dim3(256), 0, stream, logp_new,
-                       logp_old, values, v_old, adv, ret, entropy, stats, M, MB, clip_lo, clip_hi,
-                       clip, value_clip, baseline_cost, g_logp, g_value, partials);
-  else
-    hipLaunchKernelGGL(ppo_loss_kernel<1>, dim3((unsigned)nb), dim3(256), 0, stream, logp_new,
-                       logp_old, values, v_old, adv, ret, entropy, stats, M, MB, clip_lo, clip_hi,
-                       clip, value_clip, baseline_cost, g_logp, g_value, partials);
-  hipLaunchKernelGGL(ppo_finalize_kernel, dim3(1), dim3(64), 0, stream, partials, (int)nb, M,
-                     baseline_cost, entropy_cost, losses);
-  return (int)hipGetLastError();
+  const size_t M = (size_t)T * B;
+  return launch_ppo_loss(logp_new, logp_old, values, v_old, adv, ret, entropy, stats, M,
+                         M + (size_t)B, B, clip_lo, clip_hi, clip, value_clip, baseline_cost,
+                         entropy_cost, 0, g_logp, g_value, partials, losses, nullptr, stream);
 }

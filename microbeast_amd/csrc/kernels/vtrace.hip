@@ -59,39 +59,8 @@ __global__ __launch_bounds__(256) void vtrace_kernel(
       v_next = v;
     }
   }
-  // block reduction -> one partial row per block (deterministic 2-pass)
-  __shared__ float red[4][4];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  float v0 = wave_sum(s_pg), v1 = wave_sum(s_v), v2 = wave_sum(s_ent), v3 = wave_sum(s_rho);
-  if (lane == 0) { red[wave][0] = v0; red[wave][1] = v1; red[wave][2] = v2; red[wave][3] = v3; }
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    float s = 0.f;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += red[w][threadIdx.x];
-    partials[blockIdx.x * 4 + threadIdx.x] = s;
-  }
-}
-
-// losses[0..4] = pg, value, entropy, total, mean_rho
-__global__ __launch_bounds__(64) void vtrace_finalize_kernel(const float* __restrict__ partials,
-                                                             int nblocks, int T, int B,
-                                                             float baseline_cost,
-                                                             float entropy_cost,
-                                                             float* __restrict__ losses) {
-  const int lane = threadIdx.x;
-  float s[4] = {0, 0, 0, 0};
-  for (int i = lane; i < nblocks; i += 64)
-    for (int k = 0; k < 4; ++k) s[k] += partials[i * 4 + k];
-  for (int k = 0; k < 4; ++k) s[k] = wave_sum(s[k]);
-  if (lane == 0) {
-    const float invM = 1.f / ((float)T * (float)B);
-    const float pg = s[0] * invM, vl = baseline_cost * s[1] * invM, ent = s[2] * invM;
-    losses[0] = pg;
-    losses[1] = vl;
-    losses[2] = ent;
-    losses[3] = pg + vl - entropy_cost * ent;
-    losses[4] = s[3] * invM;
-  }
+  const float s[4] = {s_pg, s_v, s_ent, s_rho};
+  block_sums<4>(s, partials + blockIdx.x * 4);
 }
 
 // vtrace_kernel with V-trace(lambda) value targets and the UPGO policy term (Vinyals et al.
@@ -103,8 +72,11 @@ __global__ __launch_bounds__(64) void vtrace_finalize_kernel(const float* __rest
 // G_{t+1}, q_{t+1} and V_{t+1} are the previous iteration's registers: no load is added. All
 // three start at the bootstrap, whose tie (q == V) hands the first step G = q_{T-1}.
 // lambda = 1 and upgo_cost = 0 are vtrace_kernel's numbers bit for bit: the compiler's contraction
-// is off in these two kernels and every multiply-add that vtrace_kernel's code object fuses is
-// written as fmaf (the others stay apart), so the rounding does not move with the code around it.
+// is off here and in the finalize, and every multiply-add that vtrace_kernel's code object fuses
+// is written as fmaf (the others stay apart), so the rounding does not move with the code around
+// it. (One scan body, template <bool UPGO> with contraction off in both instances, computes
+// vtrace_kernel's arithmetic sequence but measured 3.4 us slower on the default path: not merged.)
+// Both scans end in block_sums<K> (common.h) and share vtrace_finalize_kernel<UPGO>.
 __global__ __launch_bounds__(256) void vtrace_upgo_kernel(
     const float* __restrict__ logp_new, const float* __restrict__ logp_old,
     const float* __restrict__ values, const float* __restrict__ reward,
@@ -157,43 +129,37 @@ __global__ __launch_bounds__(256) void vtrace_upgo_kernel(
       G_next = G;
     }
   }
-  // the same fixed order as vtrace_kernel: wave sum, LDS, one partial row per block
-  __shared__ float red[4][5];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  float v0 = wave_sum(s_pg), v1 = wave_sum(s_v), v2 = wave_sum(s_ent), v3 = wave_sum(s_rho);
-  float v4 = wave_sum(s_up);
-  if (lane == 0) {
-    red[wave][0] = v0; red[wave][1] = v1; red[wave][2] = v2; red[wave][3] = v3; red[wave][4] = v4;
-  }
-  __syncthreads();
-  if (threadIdx.x < 5) {
-    float s = 0.f;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += red[w][threadIdx.x];
-    partials[blockIdx.x * 5 + threadIdx.x] = s;
-  }
+  const float s[5] = {s_pg, s_v, s_ent, s_rho, s_up};
+  block_sums<5>(s, partials + blockIdx.x * 5);
 }
 
-// losses[0..5] = pg, value, entropy, total, mean_rho, upgo (pg: the V-trace term alone; upgo
-// unweighted; total = pg + upgo_cost * upgo + value - entropy_cost * entropy)
-__global__ __launch_bounds__(64) void vtrace_upgo_finalize_kernel(
+// losses[0..4] = pg, value, entropy, total, mean_rho; UPGO: [5] = upgo (pg: the V-trace term
+// alone; upgo unweighted; total = pg + upgo_cost * upgo + value - entropy_cost * entropy)
+template <bool UPGO>
+__global__ __launch_bounds__(64) void vtrace_finalize_kernel(
     const float* __restrict__ partials, int nblocks, int T, int B, float baseline_cost,
     float entropy_cost, float upgo_cost, float* __restrict__ losses) {
 #pragma clang fp contract(off)
+  constexpr int K = UPGO ? 5 : 4;
   const int lane = threadIdx.x;
-  float s[5] = {0, 0, 0, 0, 0};
+  float s[K] = {};
   for (int i = lane; i < nblocks; i += 64)
-    for (int k = 0; k < 5; ++k) s[k] += partials[i * 5 + k];
-  for (int k = 0; k < 5; ++k) s[k] = wave_sum(s[k]);
+    for (int k = 0; k < K; ++k) s[k] += partials[i * K + k];
+  for (int k = 0; k < K; ++k) s[k] = wave_sum(s[k]);
   if (lane == 0) {
     const float invM = 1.f / ((float)T * (float)B);
     const float pg = s[0] * invM, vl = baseline_cost * s[1] * invM, ent = s[2] * invM;
-    const float up = s[4] * invM;
+    float total = pg;
+    if constexpr (UPGO) {
+      const float up = s[K - 1] * invM;
+      total = pg + upgo_cost * up;
+      losses[5] = up;
+    }
     losses[0] = pg;
     losses[1] = vl;
     losses[2] = ent;
-    losses[3] = pg + upgo_cost * up + vl - entropy_cost * ent;
+    losses[3] = total + vl - entropy_cost * ent;
     losses[4] = s[3] * invM;
-    losses[5] = up;
   }
 }
 
@@ -217,7 +183,7 @@ extern "C" int mbk_vtrace_upgo(const float* logp_new, const float* logp_old, con
                      values, reward, done, entropy, T, B, gamma, lambda, rho_bar, c_bar,
                      pg_rho_bar, upgo_rho_bar, baseline_cost, upgo_cost, reward_clip, vs_out,
                      adv_out, upgo_out, g_logp, g_value, partials);
-  hipLaunchKernelGGL(vtrace_upgo_finalize_kernel, dim3(1), dim3(64), 0, stream, partials, nb, T,
+  hipLaunchKernelGGL(vtrace_finalize_kernel<true>, dim3(1), dim3(64), 0, stream, partials, nb, T,
                      B, baseline_cost, entropy_cost, upgo_cost, losses);
   return (int)hipGetLastError();
 }
@@ -233,7 +199,7 @@ extern "C" int mbk_vtrace(const float* logp_new, const float* logp_old, const fl
   hipLaunchKernelGGL(vtrace_kernel, dim3(nb), dim3(256), 0, stream, logp_new, logp_old, values,
                      reward, done, entropy, T, B, gamma, rho_bar, c_bar, pg_rho_bar, baseline_cost,
                      entropy_cost, reward_clip, vs_out, adv_out, g_logp, g_value, partials);
-  hipLaunchKernelGGL(vtrace_finalize_kernel, dim3(1), dim3(64), 0, stream, partials, nb, T, B,
-                     baseline_cost, entropy_cost, losses);
+  hipLaunchKernelGGL(vtrace_finalize_kernel<false>, dim3(1), dim3(64), 0, stream, partials, nb, T,
+                     B, baseline_cost, entropy_cost, 0.f, losses);
   return (int)hipGetLastError();
 }

@@ -15,6 +15,12 @@ Reference: ``PPO_learn`` (libs/utils.py:223-342) + the learner loop
 * nothing syncs the host inside ``learn`` except the optional loss readout (and PPO's
   target-KL stop, whose one-float read waits behind the step it follows:
   ``Learner._learn_ppo_steps``).
+
+The three entry points (``learn``, ``_learn_ppo``, ``_learn_ppo_steps``) share one copy of each
+piece: ``Rollout.rows`` slices the slot into ``evaluate()``'s arguments, ``_objective_kw`` builds
+the objective's keyword arguments from the hyper-parameters, ``_ppo_targets`` turns a first
+pass into (v_old, advantages), ``_ppo_full_step`` is the full-batch PPO step up to its loss, and
+``_fwd_done`` + ``_step_tail`` are every optimiser step from the "fwd" mark to the "optim" mark.
 """
 from __future__ import annotations
 
@@ -100,6 +106,31 @@ def ppo_block_order(seed: int, n_updates: int, epoch: int, K: int, shuffle: bool
     return torch.randperm(K, generator=g).tolist()
 
 
+class Rollout:
+    """One batch as ``evaluate()`` takes it: ``rows`` hands out slices and reshapes of the
+    slot's own arrays (views, no copy). ``abits``, the acting step's active-cell bitmap with
+    which the head compaction skips the mask pass, is dropped here when the model does not
+    accept it."""
+
+    def __init__(self, batch: dict, model: torch.nn.Module):
+        self.batch = batch
+        self.obs, self.mask, self.action = batch["obs"], batch["mask"], batch["action"]
+        ab = batch.get("abits")
+        self.abits = ab if ab is not None and getattr(model, "accepts_abits", False) else None
+        T1, self.B = batch["logp"].shape[:2]
+        self.T = T1 - 1
+        self.cuda = batch["logp"].is_cuda
+
+    def rows(self, t0: int, t1: int, n_val: int):
+        """evaluate()'s arguments for rows [t0, t1) scored, values on [t0, t0 + n_val)"""
+        obs, mask, action, ab = self.obs, self.mask, self.action, self.abits
+        n = (t1 - t0) * self.B
+        kw = {} if ab is None else {"abits": ab[t0:t1].reshape(n, ab.shape[-1])}
+        return (obs[t0:t0 + n_val].reshape(n_val * self.B, *obs.shape[2:]),
+                mask[t0:t1].reshape(n, mask.shape[2], mask.shape[-1]),
+                action[t0:t1].reshape(n, mask.shape[2], action.shape[-1])), kw
+
+
 class Learner:
     def __init__(self, model: torch.nn.Module, hp: LearnerHParams, device: torch.device,
                  info: DistInfo | None = None):
@@ -135,59 +166,20 @@ class Learner:
             return self._learn_ppo(batch, sync_timing)
         t0 = time.perf_counter()
         self.phases.start()
-        obs, mask, action = batch["obs"], batch["mask"], batch["action"]
-        T1, B = batch["logp"].shape[:2]
-        T = T1 - 1
+        ro = Rollout(batch, self.model)
+        T, B = ro.T, ro.B
         self.flat.zero_grad()
         self.reducer.start_step()
-        flat_obs = obs.reshape(T1 * B, *obs.shape[2:])
-        S = mask.shape[2]
-        m = mask[:T].reshape(T * B, S, mask.shape[-1])
-        a = action[:T].reshape(T * B, S, action.shape[-1])
-        kw = {}
-        ab = batch.get("abits")
-        if ab is not None and getattr(self.model, "accepts_abits", False):
-            # the acting step's active-cell bitmap: the head compaction skips the mask pass
-            kw["abits"] = ab[:T].reshape(T * B, ab.shape[-1])
-        logp, ent, value = self.model.evaluate(flat_obs, m, a, n_score=T * B, **kw)
-        if self.hp.vtrace_lambda == 1.0 and self.hp.upgo_cost == 0.0:
-            vt = vtrace(logp.view(T, B), batch["logp"][:T], value.view(T1, B), batch["reward"][:T],
-                        batch["done"][:T], ent.view(T, B), gamma=self.hp.gamma, rho_bar=self.hp.rho_bar,
-                        c_bar=self.hp.c_bar, pg_rho_bar=self.hp.pg_rho_bar,
-                        baseline_cost=self.hp.baseline_cost, entropy_cost=self.hp.entropy_cost,
-                        reward_clip=self.hp.reward_clip, ws=self.ws)
-        else:  # V-trace(lambda) targets and / or the UPGO term: losses [6]
-            vt = vtrace_upgo(logp.view(T, B), batch["logp"][:T], value.view(T1, B),
-                             batch["reward"][:T], batch["done"][:T], ent.view(T, B),
-                             gamma=self.hp.gamma, rho_bar=self.hp.rho_bar, c_bar=self.hp.c_bar,
-                             pg_rho_bar=self.hp.pg_rho_bar, baseline_cost=self.hp.baseline_cost,
-                             entropy_cost=self.hp.entropy_cost, reward_clip=self.hp.reward_clip,
-                             lam=self.hp.vtrace_lambda, upgo_cost=self.hp.upgo_cost,
-                             upgo_rho_bar=self.hp.upgo_rho_bar, ws=self.ws)
-        self.phases.mark("fwd")
-        if sync_timing and logp.is_cuda:
-            torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        torch.autograd.backward(
-            [logp, value, ent], [vt.g_logp.reshape(-1), vt.g_value.reshape(-1),
-                                 self._const_grad(ent, vt.g_ent)])
-        if self.flat.adopt_grads() and self.info.enabled:
-            raise RuntimeError("a direct-gradient parameter's gradient was not written into "
-                               "its flat slot; its all-reduce bucket went out stale")
-        self.phases.mark("bwd")
-        self.reducer.finish()
-        self.phases.mark("allreduce")
-        if sync_timing and logp.is_cuda:
-            torch.cuda.synchronize()
-        t2 = time.perf_counter()
-        self.opt.step(grad_scale=self.reducer.grad_scale)
-        self.phases.mark("optim")
-        if sync_timing and logp.is_cuda:
-            torch.cuda.synchronize()
-        t3 = time.perf_counter()
-        self.n_updates += 1
-        self.last_opt_steps = 1
-        self.timing = {"fwd_s": t1 - t0, "bwd_allreduce_s": t2 - t1, "optim_s": t3 - t2}
+        args, kw = ro.rows(0, T, T + 1)
+        logp, ent, value = self.model.evaluate(*args, n_score=T * B, **kw)
+        # V-trace(lambda) targets and / or the UPGO term: vtrace_upgo, losses [6]
+        upgo = self.hp.vtrace_lambda != 1.0 or self.hp.upgo_cost != 0.0
+        vt = (vtrace_upgo if upgo else vtrace)(
+            logp.view(T, B), batch["logp"][:T], value.view(T + 1, B), batch["reward"][:T],
+            batch["done"][:T], ent.view(T, B), ws=self.ws, **self._objective_kw(upgo))
+        t1 = self._fwd_done(sync_timing, ro.cuda)
+        t2, t3 = self._step_tail(logp, value, ent, vt, sync_timing, ro.cuda)
+        self._rollout_done(1, [t1 - t0, t2 - t1, t3 - t2])
         return vt.losses
 
     def _learn_ppo(self, batch: dict, sync_timing: bool = False) -> torch.Tensor:
@@ -204,66 +196,17 @@ class Learner:
         hp = self.hp
         if hp.ppo_minibatches > 1 or hp.ppo_target_kl > 0:
             return self._learn_ppo_steps(batch, sync_timing)
-        t_fwd = t_bwd = t_opt = 0.0
+        times = [0.0, 0.0, 0.0]
         self.phases.start()
-        obs, mask, action = batch["obs"], batch["mask"], batch["action"]
-        T1, B = batch["logp"].shape[:2]
-        T = T1 - 1
-        flat_obs = obs.reshape(T1 * B, *obs.shape[2:])
-        S = mask.shape[2]
-        m = mask[:T].reshape(T * B, S, mask.shape[-1])
-        a = action[:T].reshape(T * B, S, action.shape[-1])
-        kw = {}
-        ab = batch.get("abits")
-        if ab is not None and getattr(self.model, "accepts_abits", False):
-            kw["abits"] = ab[:T].reshape(T * B, ab.shape[-1])
-        cuda = batch["logp"].is_cuda
-        g = v_old = None
-        for epoch in range(hp.ppo_epochs):
-            t0 = time.perf_counter()
-            self.flat.zero_grad()
-            self.reducer.start_step()
-            logp, ent, value = self.model.evaluate(flat_obs, m, a, n_score=T * B, **kw)
-            if epoch == 0 and hp.ppo_adv == "vtrace":
-                v_old, g = self._vtrace_adv(batch, value, logp, T1, B, cuda)
-            elif epoch == 0:
-                if cuda:  # (a workspace buffer: the forward's own output is rewritten per epoch)
-                    v_old = self.ws.get("ppo_v_old", (T1, B), value.device)
-                    v_old.copy_(value.detach().view(T1, B))
-                else:
-                    v_old = value.detach().float().view(T1, B).clone()
-                g = gae(v_old, batch["reward"][:T], batch["done"][:T], gamma=hp.gamma,
-                        lam=hp.gae_lambda, reward_clip=hp.reward_clip, norm_adv=hp.ppo_norm_adv,
-                        ws=self.ws)
-            out = ppo_loss(logp.view(T, B), batch["logp"][:T], value.view(T1, B), v_old, g.adv,
-                           g.ret, g.stats, ent.view(T, B), clip=hp.ppo_clip,
-                           value_clip=hp.ppo_value_clip, baseline_cost=hp.baseline_cost,
-                           entropy_cost=hp.entropy_cost, ws=self.ws)
-            self.phases.mark("fwd")
-            if sync_timing and cuda:
-                torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            torch.autograd.backward(
-                [logp, value, ent], [out.g_logp.reshape(-1), out.g_value.reshape(-1),
-                                     self._const_grad(ent, out.g_ent)])
-            if self.flat.adopt_grads() and self.info.enabled:
-                raise RuntimeError("a direct-gradient parameter's gradient was not written into "
-                                   "its flat slot; its all-reduce bucket went out stale")
-            self.phases.mark("bwd")
-            self.reducer.finish()
-            self.phases.mark("allreduce")
-            if sync_timing and cuda:
-                torch.cuda.synchronize()
-            t2 = time.perf_counter()
-            self.opt.step(grad_scale=self.reducer.grad_scale)
-            self.phases.mark("optim")
-            if sync_timing and cuda:
-                torch.cuda.synchronize()
-            t3 = time.perf_counter()
-            t_fwd, t_bwd, t_opt = t_fwd + t1 - t0, t_bwd + t2 - t1, t_opt + t3 - t2
-        self.n_updates += 1
-        self.last_opt_steps = hp.ppo_epochs
-        self.timing = {"fwd_s": t_fwd, "bwd_allreduce_s": t_bwd, "optim_s": t_opt}
+        ro = Rollout(batch, self.model)
+        targets = None
+        for _ in range(hp.ppo_epochs):
+            t0 = self._step_begin()
+            logp, ent, value, out, targets = self._ppo_full_step(ro, targets)
+            t1 = self._fwd_done(sync_timing, ro.cuda)
+            t2, t3 = self._step_tail(logp, value, ent, out, sync_timing, ro.cuda)
+            times = [times[0] + t1 - t0, times[1] + t2 - t1, times[2] + t3 - t2]
+        self._rollout_done(hp.ppo_epochs, times)
         return out.losses
 
     def _learn_ppo_steps(self, batch: dict, sync_timing: bool = False) -> torch.Tensor:
@@ -274,9 +217,9 @@ class Learner:
         K blocks of T / K consecutive rows (all envs) once, in ``ppo_block_order``'s order, and
         each visit is a full optimiser step on that block alone: zero grads -> forward on the
         block's rows (no bootstrap row) -> block loss -> backward -> all-reduce -> Adam. K == 1
-        keeps ``_learn_ppo``'s steps (epoch 0's own values are ``v_old``). ``ppo_adv="vtrace"``:
-        the pre-pass is a no-grad ``evaluate`` over the slot, whose log-probs the V-trace(lambda)
-        scan needs beside the values (``_vtrace_adv``).
+        keeps ``_learn_ppo``'s steps (``_ppo_full_step``: epoch 0's own values are ``v_old``).
+        ``ppo_adv="vtrace"``: the pre-pass is a no-grad ``evaluate`` over the slot, whose
+        log-probs the V-trace(lambda) scan needs beside the values (``_vtrace_adv``).
 
         ``ppo_target_kl`` > 0: the host reads a step's approx_kl only AFTER that step's
         backward, all-reduce and Adam are queued (an event recorded behind the loss launch and
@@ -286,101 +229,44 @@ class Learner:
         over the steps of the last epoch entered; K == 1: the last step's."""
         hp = self.hp
         K = hp.ppo_minibatches
-        t_fwd = t_bwd = t_opt = 0.0
+        times = [0.0, 0.0, 0.0]
         self.phases.start()
-        obs, mask, action = batch["obs"], batch["mask"], batch["action"]
-        T1, B = batch["logp"].shape[:2]
-        T = T1 - 1
+        ro = Rollout(batch, self.model)
+        T, B = ro.T, ro.B
         if T % K != 0:
             raise ValueError(f"--ppo_minibatches {K} does not divide the unroll length {T}")
         Tm = T // K
-        S = mask.shape[2]
-        ab = batch.get("abits")
-        if ab is not None and not getattr(self.model, "accepts_abits", False):
-            ab = None
-
-        def rows(t0, t1, n_val):
-            """evaluate()'s arguments for rows [t0, t1) scored, values on [t0, t0 + n_val)"""
-            kw = {} if ab is None else {"abits": ab[t0:t1].reshape((t1 - t0) * B, ab.shape[-1])}
-            return (obs[t0:t0 + n_val].reshape(n_val * B, *obs.shape[2:]),
-                    mask[t0:t1].reshape((t1 - t0) * B, S, mask.shape[-1]),
-                    action[t0:t1].reshape((t1 - t0) * B, S, action.shape[-1])), kw
-
-        cuda = batch["logp"].is_cuda
-        g = v_old = stats = mean = None
+        targets = stats = mean = None
         if K > 1:
-            args, kw = rows(0, T, T1)
-            if hp.ppo_adv == "vtrace":  # the scan needs the pass's log-probs too
-                with torch.no_grad():
+            args, kw = ro.rows(0, T, T + 1)
+            with torch.no_grad():
+                if hp.ppo_adv != "vtrace" and hasattr(self.model, "values"):
+                    lp, v = None, self.model.values(args[0])
+                else:  # (the V-trace scan needs the pass's log-probs too)
                     lp, _, v = self.model.evaluate(*args, n_score=T * B, **kw)
-                v_old, g = self._vtrace_adv(batch, v, lp, T1, B, cuda)
-            else:
-                with torch.no_grad():
-                    if hasattr(self.model, "values"):
-                        v = self.model.values(args[0])
-                    else:
-                        v = self.model.evaluate(*args, n_score=T * B, **kw)[2]
-                v_old = self._snapshot_values(v, T1, B, cuda)
-                g = gae(v_old, batch["reward"][:T], batch["done"][:T], gamma=hp.gamma,
-                        lam=hp.gae_lambda, reward_clip=hp.reward_clip,
-                        norm_adv=hp.ppo_norm_adv, ws=self.ws)
-            stats = adv_stats_rows(g.adv, K, hp.ppo_norm_adv, ws=self.ws)
+            targets = self._ppo_targets(ro, v, lp)
+            stats = adv_stats_rows(targets[1].adv, K, hp.ppo_norm_adv, ws=self.ws)
         steps, stop = 0, False
         for epoch in range(hp.ppo_epochs):
             order = ppo_block_order(hp.ppo_seed, self.n_updates, epoch, K, hp.ppo_shuffle)
             for j, k in enumerate(order):
-                t0 = time.perf_counter()
-                self.flat.zero_grad()
-                self.reducer.start_step()
+                t0 = self._step_begin()
                 if K == 1:
-                    args, kw = rows(0, T, T1)
-                    logp, ent, value = self.model.evaluate(*args, n_score=T * B, **kw)
-                    if epoch == 0 and hp.ppo_adv == "vtrace":
-                        v_old, g = self._vtrace_adv(batch, value, logp, T1, B, cuda)
-                    elif epoch == 0:
-                        v_old = self._snapshot_values(value, T1, B, cuda)
-                        g = gae(v_old, batch["reward"][:T], batch["done"][:T], gamma=hp.gamma,
-                                lam=hp.gae_lambda, reward_clip=hp.reward_clip,
-                                norm_adv=hp.ppo_norm_adv, ws=self.ws)
-                    out = ppo_loss(logp.view(T, B), batch["logp"][:T], value.view(T1, B), v_old,
-                                   g.adv, g.ret, g.stats, ent.view(T, B), clip=hp.ppo_clip,
-                                   value_clip=hp.ppo_value_clip, baseline_cost=hp.baseline_cost,
-                                   entropy_cost=hp.entropy_cost, ws=self.ws)
+                    logp, ent, value, out, targets = self._ppo_full_step(ro, targets)
                     mean = out.losses
                 else:
-                    r0 = k * Tm
-                    args, kw = rows(r0, r0 + Tm, Tm)
+                    r0, (v_old, g) = k * Tm, targets
+                    args, kw = ro.rows(r0, r0 + Tm, Tm)
                     logp, ent, value = self.model.evaluate(*args, n_score=Tm * B, **kw)
                     out = ppo_loss_rows(logp.view(Tm, B), batch["logp"][:T], value.view(Tm, B),
                                         v_old, g.adv, g.ret, stats[k], r0, ent.view(Tm, B),
-                                        clip=hp.ppo_clip, value_clip=hp.ppo_value_clip,
-                                        baseline_cost=hp.baseline_cost,
-                                        entropy_cost=hp.entropy_cost, step=j, epoch_mean=mean,
-                                        ws=self.ws)
+                                        step=j, epoch_mean=mean, ws=self.ws,
+                                        **self._objective_kw())
                     mean = out.epoch_mean
                 kl_ev = self._kl_record(out.losses) if hp.ppo_target_kl > 0 else None
-                self.phases.mark("fwd")
-                if sync_timing and cuda:
-                    torch.cuda.synchronize()
-                t1 = time.perf_counter()
-                torch.autograd.backward(
-                    [logp, value, ent], [out.g_logp.reshape(-1), out.g_value.reshape(-1),
-                                         self._const_grad(ent, out.g_ent)])
-                if self.flat.adopt_grads() and self.info.enabled:
-                    raise RuntimeError("a direct-gradient parameter's gradient was not written "
-                                       "into its flat slot; its all-reduce bucket went out stale")
-                self.phases.mark("bwd")
-                self.reducer.finish()
-                self.phases.mark("allreduce")
-                if sync_timing and cuda:
-                    torch.cuda.synchronize()
-                t2 = time.perf_counter()
-                self.opt.step(grad_scale=self.reducer.grad_scale)
-                self.phases.mark("optim")
-                if sync_timing and cuda:
-                    torch.cuda.synchronize()
-                t3 = time.perf_counter()
-                t_fwd, t_bwd, t_opt = t_fwd + t1 - t0, t_bwd + t2 - t1, t_opt + t3 - t2
+                t1 = self._fwd_done(sync_timing, ro.cuda)
+                t2, t3 = self._step_tail(logp, value, ent, out, sync_timing, ro.cuda)
+                times = [times[0] + t1 - t0, times[1] + t2 - t1, times[2] + t3 - t2]
                 steps += 1
                 # the step above is queued (and applied) whatever its KL says
                 if hp.ppo_target_kl > 0 and self._kl_read(out.losses, kl_ev) > hp.ppo_target_kl:
@@ -388,10 +274,92 @@ class Learner:
                     break
             if stop:
                 break
+        self._rollout_done(steps, times)
+        return mean
+
+    def _objective_kw(self, upgo: bool = False) -> dict:
+        """The objective's keyword arguments, plain floats from ``hp``: ``ppo_loss`` /
+        ``ppo_loss_rows``'s under ``algo="ppo"``, else ``vtrace``'s (``upgo``: those of
+        ``vtrace_upgo``)."""
+        hp = self.hp
+        if hp.algo == "ppo":
+            return dict(clip=hp.ppo_clip, value_clip=hp.ppo_value_clip,
+                        baseline_cost=hp.baseline_cost, entropy_cost=hp.entropy_cost)
+        kw = dict(gamma=hp.gamma, rho_bar=hp.rho_bar, c_bar=hp.c_bar, pg_rho_bar=hp.pg_rho_bar,
+                  baseline_cost=hp.baseline_cost, entropy_cost=hp.entropy_cost,
+                  reward_clip=hp.reward_clip)
+        if upgo:
+            kw.update(lam=hp.vtrace_lambda, upgo_cost=hp.upgo_cost, upgo_rho_bar=hp.upgo_rho_bar)
+        return kw
+
+    def _step_begin(self) -> float:
+        """the head of one PPO optimiser step; returns its host start time"""
+        t0 = time.perf_counter()
+        self.flat.zero_grad()
+        self.reducer.start_step()
+        return t0
+
+    def _fwd_done(self, sync_timing: bool, cuda: bool) -> float:
+        """behind the loss launch (and ``_kl_record``): the "fwd" mark and the host time t1"""
+        self.phases.mark("fwd")
+        if sync_timing and cuda:
+            torch.cuda.synchronize()
+        return time.perf_counter()
+
+    def _step_tail(self, logp, value, ent, out, sync_timing: bool, cuda: bool):
+        """The rest of every optimiser step, behind ``_fwd_done``: backward seeded with the
+        objective's gradients (``out.g_logp`` / ``g_value`` / the constant ``g_ent``) ->
+        all-reduce -> Adam. Returns the host times (t2, t3) after the all-reduce and after Adam."""
+        torch.autograd.backward(
+            [logp, value, ent], [out.g_logp.reshape(-1), out.g_value.reshape(-1),
+                                 self._const_grad(ent, out.g_ent)])
+        if self.flat.adopt_grads() and self.info.enabled:
+            raise RuntimeError("a direct-gradient parameter's gradient was not written into "
+                               "its flat slot; its all-reduce bucket went out stale")
+        self.phases.mark("bwd")
+        self.reducer.finish()
+        self.phases.mark("allreduce")
+        if sync_timing and cuda:
+            torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        self.opt.step(grad_scale=self.reducer.grad_scale)
+        self.phases.mark("optim")
+        if sync_timing and cuda:
+            torch.cuda.synchronize()
+        return t2, time.perf_counter()
+
+    def _rollout_done(self, steps: int, times: list) -> None:
+        """one ``learn`` call's bookkeeping; ``times``: host seconds in fwd, bwd + all-reduce,
+        Adam"""
         self.n_updates += 1
         self.last_opt_steps = steps
-        self.timing = {"fwd_s": t_fwd, "bwd_allreduce_s": t_bwd, "optim_s": t_opt}
-        return mean
+        self.timing = dict(zip(("fwd_s", "bwd_allreduce_s", "optim_s"), times))
+
+    def _ppo_full_step(self, ro: Rollout, targets):
+        """One full-batch PPO step up to its loss: forward on the whole rollout, the rollout's
+        targets from this pass where there are none yet (epoch 0), ``ppo_loss``. Returns
+        (logp, ent, value, out, targets)."""
+        T, B, batch = ro.T, ro.B, ro.batch
+        args, kw = ro.rows(0, T, T + 1)
+        logp, ent, value = self.model.evaluate(*args, n_score=T * B, **kw)
+        if targets is None:
+            targets = self._ppo_targets(ro, value, logp)
+        v_old, g = targets
+        out = ppo_loss(logp.view(T, B), batch["logp"][:T], value.view(T + 1, B), v_old, g.adv,
+                       g.ret, g.stats, ent.view(T, B), ws=self.ws, **self._objective_kw())
+        return logp, ent, value, out, targets
+
+    def _ppo_targets(self, ro: Rollout, value: torch.Tensor, logp):
+        """The rollout's (v_old, GaeOut) from its first pass's values [(T+1) B] and log-probs
+        (``ppo_adv="gae"`` reads none: None will do): the V-trace(lambda) scan, or a value
+        snapshot and GAE."""
+        hp, T, batch = self.hp, ro.T, ro.batch
+        if hp.ppo_adv == "vtrace":
+            return self._vtrace_adv(batch, value, logp, T + 1, ro.B, ro.cuda)
+        v_old = self._snapshot_values(value, T + 1, ro.B, ro.cuda)
+        return v_old, gae(v_old, batch["reward"][:T], batch["done"][:T], gamma=hp.gamma,
+                          lam=hp.gae_lambda, reward_clip=hp.reward_clip,
+                          norm_adv=hp.ppo_norm_adv, ws=self.ws)
 
     def _snapshot_values(self, value: torch.Tensor, T1: int, B: int, cuda: bool) -> torch.Tensor:
         """detached fp32 [T1, B] copy of a forward's values (on a GPU: a workspace buffer)"""

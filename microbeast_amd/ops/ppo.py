@@ -77,7 +77,7 @@ from dataclasses import dataclass
 import torch
 
 from .. import _native as N
-from .vtrace import VTraceWorkspace
+from .vtrace import VTraceWorkspace, f32c
 
 
 @dataclass
@@ -222,6 +222,13 @@ def ppo_loss_rows_torch(logp_new, logp_old, values, v_old, adv, ret, stats, t0: 
     return PPOOut(o.g_logp, o.g_value, o.g_ent, o.losses, adv, ret, mean)
 
 
+def _loss_inputs(logp_new, logp_old, values, v_old, adv, ret, stats, entropy):
+    """``mbk_ppo_loss`` / ``mbk_ppo_loss_rows``'s input arrays, detached contiguous fp32: the seven
+    in the launchers' order, then the entropy or None"""
+    arrays = [f32c(x.detach()) for x in (logp_new, logp_old, values, v_old, adv, ret, stats)]
+    return (*arrays, f32c(entropy.detach()) if entropy is not None else None)
+
+
 def gae(v_old, reward, done, gamma=0.99, lam=0.95, reward_clip=0.0, norm_adv=True,
         ws: VTraceWorkspace | None = None) -> GaeOut:
     """v_old: [T+1, B]; reward / done: [T, B]. The outputs live in ``ws`` (reused by the next
@@ -235,8 +242,7 @@ def gae(v_old, reward, done, gamma=0.99, lam=0.95, reward_clip=0.0, norm_adv=Tru
     ret = ws.get("ppo_ret", (T, B), dev)
     partials = ws.get("ppo_gae_partials", (((B + 255) // 256) * 3,), dev)
     stats = ws.get("ppo_stats", (2,), dev)
-    vo = v_old.detach().float().contiguous()
-    rew = reward.float().contiguous()
+    vo, rew = f32c(v_old.detach()), f32c(reward)
     dn = done.to(torch.uint8).contiguous()
     N.check(N.kernels().mbk_gae(vo.data_ptr(), rew.data_ptr(), dn.data_ptr(), T, B, gamma, lam,
                                 reward_clip, int(bool(norm_adv)), adv.data_ptr(), ret.data_ptr(),
@@ -260,8 +266,7 @@ def vtrace_adv(logp_pi, logp_mu, v, reward, done, gamma=0.99, lam=0.95, rho_bar=
     partials = ws.get("ppo_vt_partials", (((B + 255) // 256) * 6,), dev)
     stats = ws.get("ppo_vt_stats", (2,), dev)
     is_stats = ws.get("ppo_vt_is_stats", (3,), dev)
-    c = lambda x: x.detach().float().contiguous()  # noqa: E731
-    lpi, lmu, vo, rew = c(logp_pi), c(logp_mu), c(v), c(reward)
+    lpi, lmu, vo, rew = (f32c(x.detach()) for x in (logp_pi, logp_mu, v, reward))
     dn = done.to(torch.uint8).contiguous()
     if not (lpi.shape == lmu.shape == dn.shape == (T, B)) or vo.numel() != (T + 1) * B:
         raise ValueError("vtrace_adv: logp_pi / logp_mu / done [T, B] and v [T+1, B] expected")
@@ -288,10 +293,8 @@ def ppo_loss(logp_new, logp_old, values, v_old, adv, ret, stats, entropy=None, c
     g_value = ws.get("ppo_g_value", (T + 1, B), dev)
     partials = ws.get("ppo_partials", ((((T + 1) * B + 255) // 256) * 6,), dev)
     losses = ws.get("ppo_losses", (7,), dev)
-    c = lambda x: x.detach().float().contiguous()  # noqa: E731
-    lpn, lpo, val, vo, ad, rt, st = (c(logp_new), c(logp_old), c(values), c(v_old), c(adv),
-                                     c(ret), c(stats))
-    ent = c(entropy) if entropy is not None else None
+    lpn, lpo, val, vo, ad, rt, st, ent = _loss_inputs(logp_new, logp_old, values, v_old, adv,
+                                                      ret, stats, entropy)
     N.check(N.kernels().mbk_ppo_loss(
         lpn.data_ptr(), lpo.data_ptr(), val.data_ptr(), vo.data_ptr(), ad.data_ptr(),
         rt.data_ptr(), N.ptr(ent), st.data_ptr(), T, B, 1.0 - clip, 1.0 + clip, clip, value_clip,
@@ -313,7 +316,7 @@ def adv_stats_rows(adv, K: int, norm_adv=True, ws: VTraceWorkspace | None = None
     nb = min(256, ((T // K) * B + 255) // 256)
     partials = ws.get("ppo_rows_stats_partials", (K * nb * 3,), dev)
     stats = ws.get("ppo_rows_stats", (K, 2), dev)
-    ad = adv.detach().float().contiguous()
+    ad = f32c(adv.detach())
     N.check(N.kernels().mbk_adv_stats_rows(ad.data_ptr(), T, B, K, int(bool(norm_adv)),
                                            partials.data_ptr(), stats.data_ptr(),
                                            N.stream_ptr()), "adv_stats_rows")
@@ -344,10 +347,8 @@ def ppo_loss_rows(logp_new, logp_old, values, v_old, adv, ret, stats, t0: int, e
     partials = ws.get("ppo_rows_partials", (((Tm * B + 255) // 256) * 6,), dev)
     losses = ws.get("ppo_rows_losses", (7,), dev)
     mean = ws.get("ppo_epoch_mean", (7,), dev)
-    c = lambda x: x.detach().float().contiguous()  # noqa: E731
-    lpn, lpo, val, vo, ad, rt, st = (c(logp_new), c(logp_old), c(values), c(v_old), c(adv),
-                                     c(ret), c(stats))
-    ent = c(entropy) if entropy is not None else None
+    lpn, lpo, val, vo, ad, rt, st, ent = _loss_inputs(logp_new, logp_old, values, v_old, adv,
+                                                      ret, stats, entropy)
     N.check(N.kernels().mbk_ppo_loss_rows(
         lpn.data_ptr(), lpo.data_ptr(), val.data_ptr(), vo.data_ptr(), ad.data_ptr(),
         rt.data_ptr(), N.ptr(ent), st.data_ptr(), t0, Tm, B, 1.0 - clip, 1.0 + clip, clip,

@@ -83,6 +83,19 @@ class VTraceWorkspace:
         return t
 
 
+def f32c(x):
+    """x as a contiguous fp32 tensor: x itself where it already is one (no copy, no launch)"""
+    return x.float().contiguous()
+
+
+def _launch_inputs(logp_new, logp_old, values, reward, done, entropy):
+    """``mbk_vtrace`` / ``mbk_vtrace_upgo``'s input arrays: contiguous fp32, done as uint8, the
+    learner's own outputs detached; entropy may be None"""
+    return (f32c(logp_new.detach()), f32c(logp_old), f32c(values.detach()), f32c(reward),
+            done.to(torch.uint8).contiguous(),
+            f32c(entropy.detach()) if entropy is not None else None)
+
+
 def vtrace(logp_new, logp_old, values, reward, done, entropy=None, gamma=0.99, rho_bar=1.0,
            c_bar=1.0, pg_rho_bar=1.0, baseline_cost=0.5, entropy_cost=0.01, reward_clip=0.0,
            want_targets=False, ws: VTraceWorkspace | None = None) -> VTraceOut:
@@ -99,10 +112,7 @@ def vtrace(logp_new, logp_old, values, reward, done, entropy=None, gamma=0.99, r
     losses = ws.get("losses", (5,), dev)
     vs = ws.get("vs", (T, B), dev) if want_targets else None
     adv = ws.get("adv", (T, B), dev) if want_targets else None
-    c = lambda x: x.contiguous()  # noqa: E731
-    lpn, lpo, val, rew = c(logp_new.detach().float()), c(logp_old.float()), c(values.detach().float()), c(reward.float())
-    dn = c(done.to(torch.uint8))
-    ent = c(entropy.detach().float()) if entropy is not None else None
+    lpn, lpo, val, rew, dn, ent = _launch_inputs(logp_new, logp_old, values, reward, done, entropy)
     N.check(N.kernels().mbk_vtrace(
         lpn.data_ptr(), lpo.data_ptr(), val.data_ptr(), rew.data_ptr(), dn.data_ptr(),
         N.ptr(ent), T, B, gamma, rho_bar, c_bar, pg_rho_bar, baseline_cost, entropy_cost,
@@ -192,10 +202,7 @@ def vtrace_upgo(logp_new, logp_old, values, reward, done, entropy=None, gamma=0.
     vs = ws.get("upgo_vs", (T, B), dev) if want_targets else None
     adv = ws.get("upgo_adv", (T, B), dev) if want_targets else None
     G = ws.get("upgo_ret", (T, B), dev) if want_targets else None
-    c = lambda x: x.contiguous()  # noqa: E731
-    lpn, lpo, val, rew = c(logp_new.detach().float()), c(logp_old.float()), c(values.detach().float()), c(reward.float())
-    dn = c(done.to(torch.uint8))
-    ent = c(entropy.detach().float()) if entropy is not None else None
+    lpn, lpo, val, rew, dn, ent = _launch_inputs(logp_new, logp_old, values, reward, done, entropy)
     N.check(N.kernels().mbk_vtrace_upgo(
         lpn.data_ptr(), lpo.data_ptr(), val.data_ptr(), rew.data_ptr(), dn.data_ptr(),
         N.ptr(ent), T, B, gamma, lam, rho_bar, c_bar, pg_rho_bar, upgo_rho_bar, baseline_cost,

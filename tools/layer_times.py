@@ -3,7 +3,7 @@
 HBM bytes each trunk layer must move at least (from its role in ops/encoder.py), so each
 conv reads as an achieved-bandwidth / MFMA-rate figure.
 
-    python tools/layer_times.py <rocprof_dir> [--last_kernel vtrace_kernel] [--n 120]
+    python tools/layer_times.py <rocprof_dir> [--out FILE]
 
 The last update is found as the dispatches between the second-to-last and the last
 ``adam_kernel`` (the optimizer closes every update).
