@@ -116,6 +116,20 @@ __device__ __forceinline__ float u01(uint32_t x) {  // (0,1]
   return ((float)(x >> 8) + 1.0f) * (1.0f / 16777216.0f);
 }
 
+// The kComps uniforms of one cell's sampling step, the one stream every sampling kernel draws
+// from: counter {cell lo, cell hi, step lo, step hi}, key = seed, a second draw at
+// counter.y ^ 0x80000000 for components 4..6. (head.hip calls this; masked_cell.hip's two
+// kernels write the same draw out on their int64 cell index, which compiles to other code.)
+__device__ __forceinline__ void cell_uniforms(size_t cell, uint64_t seed, uint64_t step,
+                                              float (&u)[kComps]) {
+  u32x4 ctr = {(uint32_t)cell, (uint32_t)(cell >> 32), (uint32_t)step, (uint32_t)(step >> 32)};
+  const u32x4 q0 = philox(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
+  ctr.y ^= 0x80000000u;
+  const u32x4 q1 = philox(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
+  u[0] = u01(q0.x); u[1] = u01(q0.y); u[2] = u01(q0.z); u[3] = u01(q0.w);
+  u[4] = u01(q1.x); u[5] = u01(q1.y); u[6] = u01(q1.z);
+}
+
 // ------------------------------------------------------------------ cell epilogue
 // One microRTS cell: 78 logits z (fp32, any stride-1 storage), 78 mask bits,
 // 7 categorical segments. Semantics match the reference CategoricalMasked

@@ -292,9 +292,11 @@ __device__ __forceinline__ void unit_z(const bf16* __restrict__ X, const bf16* _
   }
 }
 
-// exclusive prefix of ceil(cnt / 16) over the S <= kMaxUnitCells cells into upre (wave 0, 16
-// cells per lane; upre[kMaxUnitCells] = the unit total). Caller barriers before reading it.
+// exclusive prefix of ceil(cnt / PER) -- a cell's PER-pair work items: head_fwd's 16-pair units,
+// head_act's HA_JOB-pair jobs -- over the S <= kMaxUnitCells cells into upre (wave 0, 16 cells
+// per lane; upre[kMaxUnitCells] = the item total). Caller barriers before reading it.
 constexpr int kMaxUnitCells = 1024;
+template <int PER>
 __device__ __forceinline__ void unit_prefix(const int* __restrict__ cnt, int S, int* upre) {
   const int lane = threadIdx.x & 63;
   if ((threadIdx.x >> 6) != 0) return;
@@ -303,7 +305,7 @@ __device__ __forceinline__ void unit_prefix(const int* __restrict__ cnt, int S, 
   for (int k = 0; k < 16; ++k) {
     const int c = lane * 16 + k;
     loc[k] = run;
-    run += c < S ? (cnt[c] + 15) / 16 : 0;
+    run += c < S ? (cnt[c] + PER - 1) / PER : 0;
   }
   int x = run;  // inclusive wave scan of the lane totals
 #pragma unroll
@@ -318,6 +320,16 @@ __device__ __forceinline__ void unit_prefix(const int* __restrict__ cnt, int S, 
     if (c <= S) upre[c] = base + loc[k];
   }
   if (lane == 63) upre[kMaxUnitCells] = x;
+}
+// the cell of work item u: the last cell whose prefix <= u (cells without items share the next
+// one's prefix)
+__device__ __forceinline__ int cell_of(const int* pre, int S, int u) {
+  int lo = 0, hi = S - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (pre[mid] <= u) lo = mid; else hi = mid - 1;
+  }
+  return lo;
 }
 
 // ------------------------------------------------------------------ forward
@@ -342,7 +354,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(
   const int G = lane >> 4, li = lane & 15;
   int nunits;
   if (cnt) {
-    unit_prefix(cnt, S, upre);
+    unit_prefix<16>(cnt, S, upre);
     __syncthreads();
     nunits = upre[kMaxUnitCells];
   } else {
@@ -351,13 +363,8 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(
   float (*z)[NP + 1] = zs[wave];
   for (int u = blockIdx.x * 4 + wave; u < nunits; u += gridDim.x * 4) {
     int c, r0, gend;
-    if (cnt) {  // last cell whose prefix <= u (cells without units share the next one's)
-      int lo = 0, hi = S - 1;
-      while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (upre[mid] <= u) lo = mid; else hi = mid - 1;
-      }
-      c = lo;
+    if (cnt) {
+      c = cell_of(upre, S, u);
       r0 = c * E + 16 * (u - upre[c]);
       gend = c * E + cnt[c];
     } else {
@@ -378,13 +385,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(
       float uu[kComps];
       if constexpr (GREEDY) {
       } else if (sample) {
-        const uint64_t seed = rng[0], step = rng[1];
-        u32x4 ctr = {(uint32_t)fc, (uint32_t)(fc >> 32), (uint32_t)step, (uint32_t)(step >> 32)};
-        u32x4 q0 = philox(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
-        ctr.y ^= 0x80000000u;
-        u32x4 q1 = philox(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
-        uu[0] = u01(q0.x); uu[1] = u01(q0.y); uu[2] = u01(q0.z); uu[3] = u01(q0.w);
-        uu[4] = u01(q1.x); uu[5] = u01(q1.y); uu[6] = u01(q1.z);
+        cell_uniforms(fc, rng[0], rng[1], uu);
       } else {
 #pragma unroll
         for (int k = 0; k < kComps; ++k) a[k] = action[fc * kComps + k];
@@ -458,33 +459,6 @@ constexpr int HA_MB = MBK_HA_MB;     // 16-row blocks per job
 constexpr int HA_JOB = 16 * HA_MB;  // pairs per job
 constexpr int HA_ZS = NP + 1;       // logit tile row stride (floats): one row per lane
 
-// exclusive prefix of ceil(cnt / HA_JOB) over the S <= kMaxUnitCells cells into jpre (wave 0,
-// 16 cells per lane; jpre[kMaxUnitCells] = the job total). Caller barriers before reading it.
-__device__ __forceinline__ void job_prefix(const int* __restrict__ cnt, int S, int* jpre) {
-  const int lane = threadIdx.x & 63;
-  if ((threadIdx.x >> 6) != 0) return;
-  int loc[16], run = 0;
-#pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    const int c = lane * 16 + k;
-    loc[k] = run;
-    run += c < S ? (cnt[c] + HA_JOB - 1) / HA_JOB : 0;
-  }
-  int x = run;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  const int base = x - run;
-#pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    const int c = lane * 16 + k;
-    if (c <= S) jpre[c] = base + loc[k];
-  }
-  if (lane == 63) jpre[kMaxUnitCells] = x;
-}
-
 template <bool GREEDY>
 __device__ __forceinline__ void head_act_kernel_body(const HeadActArgs& a) {
   __shared__ float zs[HA_NW][HA_JOB * HA_ZS];
@@ -492,7 +466,7 @@ __device__ __forceinline__ void head_act_kernel_body(const HeadActArgs& a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int G = lane >> 4, li = lane & 15;
   const int S = a.S, E = a.E;
-  job_prefix(a.cnt, S, jpre);
+  unit_prefix<HA_JOB>(a.cnt, S, jpre);
   __syncthreads();
   const int njobs = jpre[kMaxUnitCells];
   const uint64_t seed = a.rng[0], step = a.step;
@@ -505,12 +479,7 @@ __device__ __forceinline__ void head_act_kernel_body(const HeadActArgs& a) {
   const int j0 = (int)((long long)njobs * xg / ng), j1 = (int)((long long)njobs * (xg + 1) / ng);
   float* zt = zs[wave];
   for (int j = j0 + bx * HA_NW + wave; j < j1; j += nbx * HA_NW) {
-    int lo = 0, hi = S - 1;  // last cell whose job prefix <= j
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (jpre[mid] <= j) lo = mid; else hi = mid - 1;
-    }
-    const int c = lo;
+    const int c = cell_of(jpre, S, j);
     const int rb = c * E + HA_JOB * (j - jpre[c]);
     const int nr = min(HA_JOB, c * E + a.cnt[c] - rb);  // rows of this job (1 .. 64)
     // this lane's pair (the epilogue's row = lane) and the MFMA rows' frames (block mb, row li)
@@ -568,14 +537,7 @@ __device__ __forceinline__ void head_act_kernel_body(const HeadActArgs& a) {
     if (mine) {
       uint8_t act[kComps];
       float uu[kComps];
-      if constexpr (!GREEDY) {
-        u32x4 ctr = {(uint32_t)fc, (uint32_t)(fc >> 32), (uint32_t)step, (uint32_t)(step >> 32)};
-        u32x4 q0 = philox(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
-        ctr.y ^= 0x80000000u;
-        u32x4 q1 = philox(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
-        uu[0] = u01(q0.x); uu[1] = u01(q0.y); uu[2] = u01(q0.z); uu[3] = u01(q0.w);
-        uu[4] = u01(q1.x); uu[5] = u01(q1.y); uu[6] = u01(q1.z);
-      }
+      if constexpr (!GREEDY) cell_uniforms(fc, seed, step, uu);
       float lp, en;
       cell_forward<GREEDY>(zt + lane * HA_ZS, m, act, true, uu, &lp, &en);
 #pragma unroll
@@ -664,7 +626,6 @@ __global__ __launch_bounds__(256) void head_pair_rowsum_kernel(const int* __rest
 }
 
 // ------------------------------------------------------------------ backward
-// ------------------------------------------------------------------ backward, v2
 // head_bwd2: 8 waves, 128-pair tiles, everything a tile needs in LDS:
 //   W_c  [96 rows][544 B]  the cell's 78 (+2 zero, +16 zero) logit rows, staged once per chunk
 //   X    [128][544 B]      the tile's gathered feature rows (next tile prefetched in registers)
@@ -695,30 +656,34 @@ template <int CTRL>
 __device__ __forceinline__ float hb_dpp(float v) {
   return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xF, 0xF, true));
 }
-// reductions over the 16 lanes of a DPP row (quad swaps, half-row mirror, row mirror) of N
+// max (MAX) or sum over the 16 lanes of a DPP row (quad swaps, half-row mirror, row mirror) of N
 // independent values, interleaved step by step (no DPP read right after its VALU write)
-constexpr int kHbDpp[4] = {0xB1, 0x4E, 0x141, 0x140};
-template <int N>
-__device__ __forceinline__ void hb_max16(float (&v)[N]) {
+template <bool MAX, int N>
+__device__ __forceinline__ void hb_reduce16(float (&v)[N]) {
 #pragma unroll
   for (int st = 0; st < 4; ++st)
 #pragma unroll
     for (int j = 0; j < N; ++j) {
       const float o = st == 0 ? hb_dpp<0xB1>(v[j]) : st == 1 ? hb_dpp<0x4E>(v[j])
                     : st == 2 ? hb_dpp<0x141>(v[j]) : hb_dpp<0x140>(v[j]);
-      v[j] = fmaxf(v[j], o);
+      v[j] = MAX ? fmaxf(v[j], o) : v[j] + o;
     }
 }
-template <int N>
-__device__ __forceinline__ void hb_sum16(float (&v)[N]) {
-#pragma unroll
-  for (int st = 0; st < 4; ++st)
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-      const float o = st == 0 ? hb_dpp<0xB1>(v[j]) : st == 1 ? hb_dpp<0x4E>(v[j])
-                    : st == 2 ? hb_dpp<0x141>(v[j]) : hb_dpp<0x140>(v[j]);
-      v[j] += o;
-    }
+
+// the aligned words holding the 7 action bytes of (frame, cell) pair fc: only words holding one
+// of them are read (never past the buffer's end). Returns ab, the byte of aw[0] the first one is
+// at; action_of selects the byte of segment k
+__device__ __forceinline__ int action_words(const uint8_t* __restrict__ action, size_t fc,
+                                            uint32_t (&aw)[3]) {
+  const size_t ab0 = fc * kComps;
+  const uint32_t* aw4 = (const uint32_t*)(action + (ab0 & ~(size_t)3));
+  aw[0] = aw4[0]; aw[1] = aw4[1]; aw[2] = (ab0 & 3) >= 2 ? aw4[2] : 0u;
+  return (int)(ab0 & 3);
+}
+__device__ __forceinline__ int action_of(const uint32_t (&aw)[3], int ab, int k) {
+  const int bi = ab + k;
+  const uint32_t w = bi < 4 ? aw[0] : bi < 8 ? aw[1] : aw[2];
+  return (int)((w >> (8 * (bi & 3))) & 0xFFu);
 }
 
 // ST: the forward's per-pair softmax statistics (head_score_kernel's stats: lse and entropy of
@@ -816,10 +781,7 @@ __global__ __launch_bounds__(64 * HB_NW, 1) void head_bwd2_kernel(
     if (mpart == 0) {
       mt[0] = mask[fc * 3]; mt[1] = mask[fc * 3 + 1]; mt[2] = mask[fc * 3 + 2];
     } else if (mpart == 1) {
-      // only words holding one of the row's 7 action bytes (never past the buffer's end)
-      const size_t ab0 = fc * kComps;
-      const uint32_t* aw4 = (const uint32_t*)(action + (ab0 & ~(size_t)3));
-      mt[0] = aw4[0]; mt[1] = aw4[1]; mt[2] = (ab0 & 3) >= 2 ? aw4[2] : 0u;
+      action_words(action, fc, mt);
     } else {
       mt[0] = __float_as_uint(g_logp[fr]);
       mt[1] = g_ent ? __float_as_uint(g_ent[fr]) : 0u;
@@ -963,6 +925,8 @@ __global__ __launch_bounds__(64 * HB_NW, 1) void head_bwd2_kernel(
           const int k = min(sk[nb], kComps - 1);
           const float lse = *(const float*)(rowp + 228 + 4 * k);
           const float H = *(const float*)(rowp + 256 + 4 * k);
+          // action_of, written out: through the helper this instantiation (256 VGPRs, 144 B
+          // of scratch) compiles to other instructions
           const int bi = ab[i] + k;
           const uint32_t wsel = bi < 4 ? aw[i][0] : bi < 8 ? aw[i][1] : aw[i][2];
           const int a = (int)((wsel >> (8 * (bi & 3))) & 0xFFu);
@@ -991,7 +955,7 @@ __global__ __launch_bounds__(64 * HB_NW, 1) void head_bwd2_kernel(
         for (int nb = nb0; nb <= nb1; ++nb)
           if (((okm >> (nb * 4 + i)) & 1u) && sk[nb] == k) mx[i] = fmaxf(mx[i], zz[nb][i]);
       }
-      hb_max16(mx);
+      hb_reduce16<true>(mx);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         float e_s = 0.f, e_sz = 0.f;
@@ -1005,16 +969,13 @@ __global__ __launch_bounds__(64 * HB_NW, 1) void head_bwd2_kernel(
         sm[2 * i] = e_s;
         sm[2 * i + 1] = e_sz;
       }
-      hb_sum16(sm);
+      hb_reduce16<false>(sm);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         // lse = log sum exp, H = entropy = lse - sum p z; p = exp(z - lse)
         const float lse = mx[i] + __logf(sm[2 * i]);
         const float H = lse - sm[2 * i + 1] * __builtin_amdgcn_rcpf(sm[2 * i]);
-        // action of segment k in this row: byte ab + k of the 3 words
-        const int bi = ab[i] + k;
-        const uint32_t wsel = bi < 4 ? aw[i][0] : bi < 8 ? aw[i][1] : aw[i][2];
-        const int a = (int)((wsel >> (8 * (bi & 3))) & 0xFFu);
+        const int a = action_of(aw[i], ab[i], k);  // byte ab + k of the row's 3 words
 #pragma unroll
         for (int nb = nb0; nb <= nb1; ++nb) {
           const bool in = ((okm >> (nb * 4 + i)) & 1u) && sk[nb] == k;
@@ -1202,7 +1163,6 @@ __global__ __launch_bounds__(64 * HS_NW, 1) void head_score_kernel(
   const int nitems = HS_IPC * totals[2];
   const int q = (nitems + (int)gridDim.x - 1) / (int)gridDim.x;
   const int i0 = (int)blockIdx.x * q, i1 = min(nitems, i0 + q);
-  const int sq = tid & 31, sr0 = tid >> 5;  // W staging: 16-byte chunk sq of rows sr0 + RS k
   float bcol[5];
   int wc = -1;
   // item cursor: the next non-empty item from it on (it == i1: none), its cell, this wave's
@@ -1236,15 +1196,13 @@ __global__ __launch_bounds__(64 * HS_NW, 1) void head_score_kernel(
     if (f >= 0) {
       const size_t fc = (size_t)f * S + c;
       m[0] = mask[fc * 3]; m[1] = mask[fc * 3 + 1]; m[2] = mask[fc * 3 + 2];
-      const size_t ab0 = fc * kComps;
-      const uint32_t* aw4 = (const uint32_t*)(action + (ab0 & ~(size_t)3));
-      aw[0] = aw4[0]; aw[1] = aw4[1]; aw[2] = (ab0 & 3) >= 2 ? aw4[2] : 0u;
-      ab = (int)(ab0 & 3);
+      ab = action_words(action, fc, aw);
     }
     nx = item_at(cu.it + 1);  // the next item's frames: in flight through this one
     if (c != wc) {  // stage W_c (rows 0..79) once per run of the cell's items
       // (rare: a workgroup's items are contiguous, so this runs once or twice per workgroup)
       constexpr int RS = 64 * HS_NW / 32;  // rows per pass
+      const int sq = tid & 31, sr0 = tid >> 5;  // 16-byte chunk sq of rows sr0 + RS k
       const uint4* src = (const uint4*)(Wp + (size_t)c * NP * KD) + sr0 * (KD / 8) + sq;
 #pragma unroll
       for (int nb = 0; nb < 5; ++nb) bcol[nb] = bp[(size_t)c * NP + nb * 16 + li];
@@ -1322,9 +1280,7 @@ __global__ __launch_bounds__(64 * HS_NW, 1) void head_score_kernel(
         ent += h;
         sl[k] = lse;
         sh[k] = h;
-        const int bi = ab + k;
-        const uint32_t w = bi < 4 ? aw[0] : bi < 8 ? aw[1] : aw[2];
-        const int a = (int)((w >> (8 * (bi & 3))) & 0xFFu);
+        const int a = action_of(aw, ab, k);
         const uint32_t mj = (uint32_t)(off + a);
         const uint32_t mwd = mj < 32 ? m[0] : mj < 64 ? m[1] : m[2];
         const bool valid = a < n && ((mwd >> (mj & 31)) & 1u);
@@ -1601,23 +1557,30 @@ extern "C" int mbk_head_units(int* bucket_cnt, int S, int E, int* grp_start, int
   return (int)hipGetLastError();
 }
 
+// head_fwd_kernel's one launch site: greedy picks the GREEDY instantiation (mode 2). List mode
+// passes the compaction's lists and cnt = null, count mode the bucket counts and null lists.
+static int launch_head_fwd(bool greedy, int grid, hipStream_t stream, const void* X, const void* Wp,
+                           const float* bp, const uint32_t* mask, uint8_t* action,
+                           const uint64_t* rng, int sample, const int* pairs, const int* unit_cell,
+                           const int* unit_row, const int* grp_start, const int* grp_count,
+                           const int* totals, int S, float* cell_lp, float* cell_ent, int pair_out,
+                           const int* cnt, int E) {
+  hipLaunchKernelGGL(greedy ? head_fwd_kernel<true> : head_fwd_kernel<false>, dim3(grid), dim3(256),
+                     0, stream, (const bf16*)X, (const bf16*)Wp, bp, mask, action, rng, sample, pairs,
+                     unit_cell, unit_row, grp_start, grp_count, totals, S, cell_lp, cell_ent,
+                     pair_out, cnt, E);
+  return (int)hipGetLastError();
+}
+
 extern "C" int mbk_head_fwd(const void* X, const void* Wp, const float* bp, const uint32_t* mask,
                             uint8_t* action, const uint64_t* rng, int sample, const int* pairs,
                             const int* unit_cell, const int* unit_row, const int* grp_start,
                             const int* grp_count, const int* totals, int S, int grid,
                             float* cell_lp, float* cell_ent, int pair_out, hipStream_t stream) {
   if (sample < 0 || sample > 2) return (int)hipErrorInvalidValue;
-  if (sample == 2)
-    hipLaunchKernelGGL(head_fwd_kernel<true>, dim3(grid), dim3(256), 0, stream, (const bf16*)X,
-                       (const bf16*)Wp, bp, mask, action, rng, sample, pairs, unit_cell, unit_row,
-                       grp_start, grp_count, totals, S, cell_lp, cell_ent, pair_out,
-                       (const int*)nullptr, 0);
-  else
-    hipLaunchKernelGGL(head_fwd_kernel<false>, dim3(grid), dim3(256), 0, stream, (const bf16*)X,
-                       (const bf16*)Wp, bp, mask, action, rng, sample, pairs, unit_cell, unit_row,
-                       grp_start, grp_count, totals, S, cell_lp, cell_ent, pair_out,
-                       (const int*)nullptr, 0);
-  return (int)hipGetLastError();
+  return launch_head_fwd(sample == 2, grid, stream, X, Wp, bp, mask, action, rng, sample, pairs,
+                         unit_cell, unit_row, grp_start, grp_count, totals, S, cell_lp, cell_ent,
+                         pair_out, nullptr, 0);
 }
 
 // Acting head on decode-bucketed pairs (cell c's pairs at bucket[c * E, + cnt[c])) without
@@ -1628,17 +1591,9 @@ extern "C" int mbk_head_fwd_counts(const void* X, const void* Wp, const float* b
                                    const int* bucket, const int* cnt, int E, int S, int grid,
                                    float* cell_lp, int greedy, hipStream_t stream) {
   if (S < 1 || S > kMaxUnitCells - 1 || !cnt) return (int)hipErrorInvalidValue;
-  if (greedy)
-    hipLaunchKernelGGL(head_fwd_kernel<true>, dim3(grid), dim3(256), 0, stream, (const bf16*)X,
-                       (const bf16*)Wp, bp, mask, action, rng, 2, bucket, (const int*)nullptr,
-                       (const int*)nullptr, (const int*)nullptr, (const int*)nullptr,
-                       (const int*)nullptr, S, cell_lp, (float*)nullptr, 0, cnt, E);
-  else
-    hipLaunchKernelGGL(head_fwd_kernel<false>, dim3(grid), dim3(256), 0, stream, (const bf16*)X,
-                       (const bf16*)Wp, bp, mask, action, rng, 1, bucket, (const int*)nullptr,
-                       (const int*)nullptr, (const int*)nullptr, (const int*)nullptr,
-                       (const int*)nullptr, S, cell_lp, (float*)nullptr, 0, cnt, E);
-  return (int)hipGetLastError();
+  return launch_head_fwd(greedy != 0, grid, stream, X, Wp, bp, mask, action, rng, greedy ? 2 : 1,
+                         bucket, nullptr, nullptr, nullptr, nullptr, nullptr, S, cell_lp, nullptr, 0,
+                         cnt, E);
 }
 
 extern "C" int mbk_head_pair_rowsum(const int* pidx, const uint32_t* abits, int F, int S,

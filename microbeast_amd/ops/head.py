@@ -6,9 +6,10 @@ pairs with at least one legal action are computed — a fully-masked cell has
 log-prob 0, entropy 0 and zero gradient in the reference's fp32 semantics, so
 skipping it changes nothing but the cost (typically 1-5 % of cells are active).
 
-Pipeline per call: compaction (3 small launches) -> grouped MFMA GEMM with
+Pipeline per call: compaction (4 small launches) -> grouped MFMA GEMM with
 the masked-softmax epilogue (sample or score) -> per-frame sums; backward:
-per-cell recompute + dZ + dX_pair + dW_c (one workgroup per cell) -> dX gather.
+recompute + dZ + dX_pair + dW_c over 512-pair chunks of a cell (one workgroup
+per CU, each a contiguous range of chunks) -> per-cell dW reduce -> dX gather.
 """
 from __future__ import annotations
 
@@ -52,7 +53,7 @@ class SparseHead:
         if F <= self._F:
             return
         S, dev = self.S, self.device
-        fb = min(256, max(8, F // 64))  # mirrors mbk_head_fb
+        fb = N.kernels().mbk_head_fb(F)  # frames per counting block
         nfb = (F + fb - 1) // fb
         self.cnt = torch.zeros(S * nfb, dtype=torch.int32, device=dev)
         self.off = torch.zeros(S * nfb, dtype=torch.int32, device=dev)
@@ -87,7 +88,8 @@ class SparseHead:
         assert F == self._bucket_E
         k = N.kernels()
         st = N.stream_ptr()
-        if act16_out is not None and self.count_units and self.S < 1024:
+        counts = act16_out is not None and self.count_units and self.S < 1024
+        if counts:
             # 2 launches: the head derives its units from the bucket counts itself, the
             # finale sums log-probs, packs the env actions and resets the counts
             N.check(k.mbk_head_fwd_counts(X.data_ptr(), self.Wp.data_ptr(), self.bp.data_ptr(),
@@ -96,27 +98,26 @@ class SparseHead:
                                           self.bucket_cnt.data_ptr(), F, self.S, self.fwd_grid,
                                           self.cell_lp.data_ptr(), int(greedy), st),
                     "head_fwd_counts")
-            N.check(k.mbk_row_sum_pack(self.cell_lp.data_ptr(), F, self.S, logp_out.data_ptr(),
-                                       rng.data_ptr(), action.data_ptr(), act16_out.data_ptr(),
-                                       self.bucket_cnt.data_ptr(), self.S, st), "row_sum_pack")
+        else:
+            N.check(k.mbk_head_units(self.bucket_cnt.data_ptr(), self.S, F,
+                                     self.grp_start.data_ptr(), self.grp_count.data_ptr(),
+                                     self.unit_cell.data_ptr(), self.unit_row.data_ptr(),
+                                     self.totals.data_ptr(), st), "head_units")
+            N.check(k.mbk_head_fwd(X.data_ptr(), self.Wp.data_ptr(), self.bp.data_ptr(),
+                                   mask_bits.data_ptr(), action.data_ptr(), rng.data_ptr(),
+                                   2 if greedy else 1, self.bucket.data_ptr(),
+                                   self.unit_cell.data_ptr(), self.unit_row.data_ptr(),
+                                   self.grp_start.data_ptr(), self.grp_count.data_ptr(),
+                                   self.totals.data_ptr(), self.S, self.fwd_grid,
+                                   self.cell_lp.data_ptr(), None, 0, st), "head_fwd")
+        if act16_out is None:
+            N.check(k.mbk_row_sum_rng(self.cell_lp.data_ptr(), F, self.S, logp_out.data_ptr(),
+                                      rng.data_ptr(), st), "row_sum_rng")
             return logp_out
-        N.check(k.mbk_head_units(self.bucket_cnt.data_ptr(), self.S, F, self.grp_start.data_ptr(),
-                                 self.grp_count.data_ptr(), self.unit_cell.data_ptr(),
-                                 self.unit_row.data_ptr(), self.totals.data_ptr(), st), "head_units")
-        N.check(k.mbk_head_fwd(X.data_ptr(), self.Wp.data_ptr(), self.bp.data_ptr(),
-                               mask_bits.data_ptr(), action.data_ptr(), rng.data_ptr(),
-                               2 if greedy else 1, self.bucket.data_ptr(), self.unit_cell.data_ptr(),
-                               self.unit_row.data_ptr(), self.grp_start.data_ptr(),
-                               self.grp_count.data_ptr(), self.totals.data_ptr(), self.S,
-                               self.fwd_grid, self.cell_lp.data_ptr(), None, 0, st),
-                "head_fwd")
-        if act16_out is not None:
-            N.check(k.mbk_row_sum_pack(self.cell_lp.data_ptr(), F, self.S, logp_out.data_ptr(),
-                                       rng.data_ptr(), action.data_ptr(), act16_out.data_ptr(),
-                                       None, 0, st), "row_sum_pack")
-            return logp_out
-        N.check(k.mbk_row_sum_rng(self.cell_lp.data_ptr(), F, self.S, logp_out.data_ptr(),
-                                  rng.data_ptr(), st), "row_sum_rng")
+        N.check(k.mbk_row_sum_pack(self.cell_lp.data_ptr(), F, self.S, logp_out.data_ptr(),
+                                   rng.data_ptr(), action.data_ptr(), act16_out.data_ptr(),
+                                   self.bucket_cnt.data_ptr() if counts else None,
+                                   self.S if counts else 0, st), "row_sum_pack")
         return logp_out
 
     def pack(self, W: torch.Tensor, b: torch.Tensor, with_t: bool):

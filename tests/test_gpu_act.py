@@ -89,7 +89,7 @@ def test_fused_act_step_bit_identical(cuda, E, sparse):
     reward = torch.randn(E, device=cuda)
     done = (torch.rand(E, device=cuda) < 0.3).to(torch.uint8)
     rdst, ddst = torch.zeros_like(reward), torch.zeros_like(done)
-    n_active = 0
+    n_active, max_cell, partial_job = 0, 0, False
     abits = torch.full((E, S // 32), -1, dtype=torch.int32, device=cuda)
     abits2 = torch.full_like(abits, -1)
     for i, (codes, res) in enumerate(_codes_stream(E, 24, seed=E)):
@@ -144,7 +144,12 @@ def test_fused_act_step_bit_identical(cuda, E, sparse):
             assert int(ws.bucket_cnt[(1 - par) * 256:(2 - par) * 256].abs().sum()) == 0
         assert int(ws.pending[:E].abs().sum()) == 0
         n_active += int((mask != 0).any(-1).sum())
+        per_cell = (mask != 0).any(-1).sum(0)  # active envs per cell: launch B's job sizes
+        max_cell = max(max_cell, int(per_cell.max()))
+        partial_job |= bool((per_cell % 64 != 0).any())
     assert n_active > 50 * 24  # the head actually sampled
+    if E == 520:  # a cell split into two 64-pair jobs, and a partial job
+        assert max_cell > 64 and partial_job
     assert int(rng_b[1]) == 7 + 24
 
 

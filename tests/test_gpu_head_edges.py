@@ -574,3 +574,91 @@ def test_sampling_frequencies(cuda):
     a = a.cpu()
     assert bool((a[:, [0, 1, 3]] == 0).all())
     hc.assert_in_band(a[:, c], m, p)
+
+
+# ------------------------------------------------------------------ count-mode units (acting)
+# Pairs per cell at the edges of head_fwd's 16-pair unit and head_act's 64-pair job; the first
+# cell, the last two and the runs 4..6 and 13..96 are empty (an empty cell shares the next one's
+# prefix: the tie of the unit search)
+UNIT_CELLS = {1: 1, 2: 15, 3: 16, 7: 17, 8: 63, 9: 0, 10: 64, 11: 65, 12: 128, 97: 129}
+UNIT_F, UNIT_S, UNIT_E = 131, 100, 130  # frames, cells, bucket stride (>= the largest count)
+
+
+def _unit_state(cuda):
+    """Hand-built buckets (cell c's frames, ascending, at bucket[c * E ..]) and the sorted path's
+    actions / per-cell log-probs of modes 1 and 2, computed once."""
+    from guarded import GuardedTorch
+    from microbeast_amd.ops.head import SparseHead
+    if "units" in _ST:
+        return _ST["units"]
+    N, k = _k()
+    F, S, E = UNIT_F, UNIT_S, UNIT_E
+    counts = [UNIT_CELLS.get(c, 0) for c in range(S)]
+    assert counts[0] == 0 and counts[-1] == 0 and max(counts) <= E
+    assert sorted(set(counts)) == [0, 1, 15, 16, 17, 63, 64, 65, 128, 129]
+    active = hc.place(counts, F, 91, special={0: []})  # frame 0: no active cell
+    mask, _, _ = hc.build_masks(active, 92)
+    gen = torch.Generator().manual_seed(93)
+    head = SparseHead(S, cuda)
+    head.pack((torch.randn(S * 78, 256, generator=gen) * 0.05).to(cuda),
+              (torch.randn(S * 78, generator=gen) * 0.1).to(cuda), with_t=False)
+    # unused bucket slots name frame 0: a slot read by mistake writes an inactive cell's output
+    bucket = torch.zeros(S, E, dtype=torch.int32)
+    for c in range(S):
+        fr = active[:, c].nonzero().flatten()
+        assert not (counts[c] == 0 and len(fr)) and not bool(active[0, c])
+        bucket[c, :len(fr)] = fr.int()
+    st = types.SimpleNamespace(
+        F=F, S=S, E=E, head=head, active=active.to(cuda), mb=hc.pack_bits(mask).to(cuda),
+        X=(torch.randn(F, 256, generator=gen) * 0.5).bfloat16().to(cuda), bucket=bucket.to(cuda),
+        cnt=torch.tensor(counts, dtype=torch.int32, device=cuda),
+        rng=torch.tensor([4711, 5], dtype=torch.int64, device=cuda), ref={})
+    head.compact(st.mb, F, None, dense_out=False)
+    for mode in (1, 2):
+        g = GuardedTorch()
+        a = g.empty(F, S, 7, dtype=torch.uint8, device=cuda, interior=False)
+        lp = g.empty(F, S, dtype=torch.float32, device=cuda, interior=False)
+        N.check(k.mbk_head_fwd(st.X.data_ptr(), head.Wp.data_ptr(), head.bp.data_ptr(),
+                               st.mb.data_ptr(), a.data_ptr(), st.rng.data_ptr(), mode,
+                               head.pairs.data_ptr(), head.unit_cell.data_ptr(),
+                               head.unit_row.data_ptr(), head.grp_start.data_ptr(),
+                               head.grp_count.data_ptr(), head.totals.data_ptr(), S, head.fwd_grid,
+                               lp.data_ptr(), None, 0, N.stream_ptr()), "head_fwd")
+        g.check()
+        assert untouched(a[~st.active]) and untouched(lp[~st.active])
+        assert not bool(torch.isnan(lp[st.active]).any()) and bool((a[st.active] <= 48).all())
+        st.ref[mode] = (a[st.active].clone(), lp[st.active].view(torch.int32).clone())
+    assert not torch.equal(st.ref[1][0], st.ref[2][0])  # sampling and arg-max differ somewhere
+    _ST["units"] = st
+    return st
+
+
+@pytest.mark.parametrize("grid", [0, 3, 1])
+@pytest.mark.parametrize("greedy", [0, 1])
+def test_count_mode_units_match_sorted_path(cuda, greedy, grid):
+    """mbk_head_fwd_counts derives its 16-pair units from the per-cell bucket counts in every
+    workgroup (unit_prefix + cell_of, the derivation head_act's jobs share): on counts at every
+    unit and job edge, with empty cells first, last and in runs, its actions and per-cell
+    log-probs equal the sorted path's (mbk_head_compact + mbk_head_fwd) bit for bit. grid 1 and
+    3: one workgroup's four waves stride over all 35 units. The counters are left alone and
+    nothing is written for an inactive cell."""
+    from guarded import GuardedTorch
+    N, k = _k()
+    st = _unit_state(cuda)
+    F, S, E, head = st.F, st.S, st.E, st.head
+    g = GuardedTorch()
+    a = g.empty(F, S, 7, dtype=torch.uint8, device=cuda, interior=False)
+    lp = g.empty(F, S, dtype=torch.float32, device=cuda, interior=False)
+    cnt = g.empty(S, dtype=torch.int32, device=cuda, interior=False)
+    cnt.copy_(st.cnt)
+    N.check(k.mbk_head_fwd_counts(st.X.data_ptr(), head.Wp.data_ptr(), head.bp.data_ptr(),
+                                  st.mb.data_ptr(), a.data_ptr(), st.rng.data_ptr(),
+                                  st.bucket.data_ptr(), cnt.data_ptr(), E, S,
+                                  grid if grid else head.fwd_grid, lp.data_ptr(), greedy,
+                                  N.stream_ptr()), "head_fwd_counts")
+    g.check()
+    assert torch.equal(cnt, st.cnt)
+    assert untouched(a[~st.active]) and untouched(lp[~st.active])
+    ra, rlp = st.ref[2 if greedy else 1]
+    assert torch.equal(a[st.active], ra)
+    assert torch.equal(lp[st.active].view(torch.int32), rlp)
