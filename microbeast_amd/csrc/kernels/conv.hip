@@ -41,13 +41,6 @@ namespace {
 
 constexpr int kThreads = 256;
 
-template <int CIN>
-struct Geo {
-  static constexpr int NCH = CIN == 16 ? 5 : 9;  // K chunks of 32
-  static constexpr int PIXB = CIN * 2 + 16;       // padded NHWC pixel stride in LDS (bytes)
-  static constexpr int PIXB8 = CIN + 8;           // fp8 tile pixel stride
-};
-
 struct ConvFwdArgs {
   const void* x;
   const bf16* w;
@@ -72,16 +65,6 @@ struct ConvFwdArgs {
 // consecutive channels of one pixel and the epilogue moves 8-byte vectors.
 constexpr int kPF = 8;
 
-__device__ __forceinline__ uint4 expand_bits8(uint32_t bits) {
-  // 8 one-hot planes -> 8 bf16 (1.0 / 0.0)
-  uint32_t w4[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    w4[j] = (((bits >> (2 * j)) & 1u) ? 0x3F80u : 0u) |
-            (((bits >> (2 * j + 1)) & 1u) ? 0x3F800000u : 0u);
-  return make_uint4(w4[0], w4[1], w4[2], w4[3]);
-}
-
 __device__ __forceinline__ uint2 expand_bits8_fp8(uint32_t bits) {
   // 8 one-hot planes -> 8 OCP e4m3 bytes (1.0 = 0x38)
   uint32_t w2[2] = {0u, 0u};
@@ -89,25 +72,6 @@ __device__ __forceinline__ uint2 expand_bits8_fp8(uint32_t bits) {
   for (int j = 0; j < 8; ++j)
     if ((bits >> j) & 1u) w2[j >> 2] |= 0x38u << (8 * (j & 3));
   return make_uint2(w2[0], w2[1]);
-}
-
-__device__ __forceinline__ uint32_t cvt_fp8x4(float a, float b, float c, float d) {
-  // round-to-nearest-even into OCP e4m3 (gfx950), saturated to +-448
-  auto sat = [](float v) { return fminf(fmaxf(v, -448.f), 448.f); };
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(sat(a), sat(b), 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(sat(c), sat(d), w, true);
-  return (uint32_t)w;
-}
-
-__device__ __forceinline__ uint2 bf16x8_to_fp8(uint4 v) {
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-  float f[8];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    f[2 * j] = __uint_as_float(w[j] << 16);
-    f[2 * j + 1] = __uint_as_float(w[j] & 0xFFFF0000u);
-  }
-  return make_uint2(cvt_fp8x4(f[0], f[1], f[2], f[3]), cvt_fp8x4(f[4], f[5], f[6], f[7]));
 }
 
 template <int CIN, bool BITS, bool F8>
@@ -160,17 +124,15 @@ __global__ __launch_bounds__(kThreads) void conv_fwd_kernel(ConvFwdArgs a) {
   // ---- weights -> registers (A fragments): lane holds w[co = nb*16 + li][c][8g..8g+7]
   Frag8 bw[NCH][NB];
   long bw8[NCH][NB];
+  if constexpr (F8) {
 #pragma unroll
-  for (int nb = 0; nb < NB; ++nb) {
-    if constexpr (F8) {
+    for (int nb = 0; nb < NB; ++nb) {
       const long* wp = (const long*)((const uint8_t*)a.w + (size_t)(nb * 16 + li) * NCH * 32 + g * 8);
 #pragma unroll
       for (int c = 0; c < NCH; ++c) bw8[c][nb] = wp[c * 4];
-    } else {
-      const uint4* wp = (const uint4*)(a.w + (size_t)(nb * 16 + li) * NCH * 32 + g * 8);
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) bw[c][nb].u = wp[c * 4];
     }
+  } else {
+    load_wfrags(bw, a.w, li, g);
   }
   float bias_v[NB][4], wsc[NB][4];
 #pragma unroll
@@ -195,10 +157,7 @@ __global__ __launch_bounds__(kThreads) void conv_fwd_kernel(ConvFwdArgs a) {
     }
   };
   auto put = [&](int off, uint4 v) {
-    if (a.relu_in) {
-      v.x = relu2(v.x); v.y = relu2(v.y);
-      v.z = relu2(v.z); v.w = relu2(v.w);
-    }
+    if (a.relu_in) v = relu8(v);
     if constexpr (F8) *(uint2*)(tile + off) = bf16x8_to_fp8(v);
     else *(uint4*)(tile + off) = v;
   };
@@ -206,7 +165,7 @@ __global__ __launch_bounds__(kThreads) void conv_fwd_kernel(ConvFwdArgs a) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       if constexpr (F8) *(uint2*)(tile + off + q * 8) = expand_bits8_fp8(bits >> (8 * q));
-      else *(uint4*)(tile + off + q * 16) = expand_bits8(bits >> (8 * q));
+      else *(uint4*)(tile + off + q * 16) = bits8_bf16(bits >> (8 * q));
     }
   };
   // per-lane byte offset of K chunk c from the block's tap-(0,0) pixel: this lane's K group
@@ -214,13 +173,7 @@ __global__ __launch_bounds__(kThreads) void conv_fwd_kernel(ConvFwdArgs a) {
   // 32); computed once instead of per chunk and block (the kernels were VALU-bound, profile 15)
   int coff[NCH];
 #pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    int tap, ch0;
-    if (CIN == 16) { tap = 2 * c + (g >> 1); ch0 = 8 * (g & 1); }
-    else { tap = c; ch0 = 8 * g; }
-    const int tapc = tap < 9 ? tap : 8;  // CIN=16 pads chunk 4 with a zero tap
-    coff[c] = ((tapc / 3) * Wp + (tapc % 3)) * PIXB + (F8 ? ch0 : ch0 * 2);
-  }
+  for (int c = 0; c < NCH; ++c) coff[c] = chunk_off(CIN, c, g, Wp, PIXB, F8 ? 1 : 2);
   if ((int)blockIdx.x < ngroups) prefetch(blockIdx.x);
   __syncthreads();  // halo zeros visible
 
@@ -308,11 +261,7 @@ __global__ __launch_bounds__(kThreads) void conv_fwd_kernel(ConvFwdArgs a) {
           for (int i = 0; i < 4; ++i)
             v[i] += __uint_as_float(((aw[i >> 1] >> (16 * (i & 1))) & 0xFFFFu) << 16);
         }
-        uint32_t o[2];
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          o[j] = (uint32_t)__bfloat16_as_ushort(f2bf(v[2 * j])) |
-                 ((uint32_t)__bfloat16_as_ushort(f2bf(v[2 * j + 1])) << 16);
+        const uint32_t o[2] = {pack2(v[0], v[1]), pack2(v[2], v[3])};
         if (a.pool) {
           // pool over the bf16-rounded values (what y_full holds)
           *(uint2*)(otile + m * OSTR + co0) = make_uint2(o[0], o[1]);
@@ -348,23 +297,6 @@ __global__ __launch_bounds__(kThreads) void conv_fwd_kernel(ConvFwdArgs a) {
 // 3x3/2 max-pool (+argmax) runs over the workgroup's images as in conv_fwd_kernel.
 constexpr int kRowImgs = kThreads / 64;  // images per workgroup iteration: one per wave
 
-__device__ __forceinline__ uint32_t dpp_shr1(uint32_t v) {  // lane x <- lane x-1 (x=0: 0)
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);
-}
-__device__ __forceinline__ uint32_t dpp_shl1(uint32_t v) {  // lane x <- lane x+1 (x=15: 0)
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x101, 0xF, 0xF, false);
-}
-__device__ __forceinline__ bf16x8 shr_px(const Frag8& f) {
-  Frag8 o;
-  o.u = make_uint4(dpp_shr1(f.u.x), dpp_shr1(f.u.y), dpp_shr1(f.u.z), dpp_shr1(f.u.w));
-  return o.v;
-}
-__device__ __forceinline__ bf16x8 shl_px(const Frag8& f) {
-  Frag8 o;
-  o.u = make_uint4(dpp_shl1(f.u.x), dpp_shl1(f.u.y), dpp_shl1(f.u.z), dpp_shl1(f.u.w));
-  return o.v;
-}
-
 // Bit-plane expansion through a 256-entry LDS table (byte -> 8 bf16, 4 KB) instead of ~24
 // VALU bit ops per row, and the kx = 0 / 2 taps from DPP-shifted 32-bit BIT words (2 DPP
 // per row instead of 8 on the expanded fragments, each needing a zeroed destination): the
@@ -373,16 +305,6 @@ __device__ __forceinline__ bf16x8 shl_px(const Frag8& f) {
 // HT == 0: runtime height, rows loaded one pair ahead.
 constexpr int kLutBytes = 256 * 16;
 
-__device__ __forceinline__ uint32_t dpp_shr1_b(uint32_t v) {  // lane x <- lane x-1 (x=0: 0)
-  return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x111, 0xF, 0xF, true);
-}
-__device__ __forceinline__ uint32_t dpp_shl1_b(uint32_t v) {  // lane x <- lane x+1 (x=15: 0)
-  return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x101, 0xF, 0xF, true);
-}
-
-struct Row3 {  // one input row's LUT offsets for pixels x-1 (l), x (c), x+1 (h) of lane x
-  uint32_t l, c, h;
-};
 struct XRow3 {  // the same row expanded: kx = 0, 1, 2 B fragments
   Frag8 f[3];
 };
@@ -474,7 +396,7 @@ __device__ __forceinline__ void conv0_row_body(const ConvFwdArgs& a) {
   const int g = lane >> 4, li = lane & 15;
   uint4* lut = (uint4*)smem;                 // [256] byte -> 8 bf16 planes
   bf16* otile = (bf16*)(smem + kLutBytes);   // [kRowImgs * HW][OSTR] conv outputs (pool mode)
-  for (int i = tid; i < 256; i += kThreads) lut[i] = expand_bits8((uint32_t)i);
+  for (int i = tid; i < 256; i += kThreads) lut[i] = bits8_bf16((uint32_t)i);
   Frag8 bw[CB][9];            // A fragments: w[co = 16 cb + li][tap][8g .. 8g+7]
 #pragma unroll
   for (int cb = 0; cb < CB; ++cb) {
@@ -494,7 +416,7 @@ __device__ __forceinline__ void conv0_row_body(const ConvFwdArgs& a) {
   // and right of lane 15 (0 = the conv's zero padding; only WIDE blocks pass others)
   auto row = [&](uint32_t bits, uint32_t bl = 0u, uint32_t bh = 0u) {
     Row3 r;
-    uint32_t lw = dpp_shr1_b(bits), hw = dpp_shl1_b(bits);
+    uint32_t lw = dpp_shr1_zero(bits), hw = dpp_shl1_zero(bits);
     if (WIDE) {
       lw = li == 0 ? bl : lw;
       hw = li == 15 ? bh : hw;
@@ -806,7 +728,7 @@ __global__ __launch_bounds__(kThreads) void conv_wgrad_kernel(ConvWgradArgs a) {
     ((uint4*)xt)[e] = make_uint4(0, 0, 0, 0);
   for (int e = tid; e < 4; e += kThreads) ((uint4*)dzero)[e] = make_uint4(0, 0, 0, 0);
   if constexpr (BITS)
-    for (int e = tid; e < 256; e += kThreads) lut[e] = expand_bits8((uint32_t)e);
+    for (int e = tid; e < 256; e += kThreads) lut[e] = bits8_bf16((uint32_t)e);
   const int xper = a.imgs * HW * XEPP, dper = a.imgs * HW * DCH;
   // UNPOOL scatter lanes (wave w = channels 4w .. 4w + 3, see the round): lane = (image of
   // the round, window k of a parity phase, channel pair)
@@ -1609,16 +1531,14 @@ struct PackJobs {
   int n;
 };
 
-__device__ __forceinline__ int nch_of(int c) { return c == 16 ? 5 : 9; }
-
 __global__ __launch_bounds__(256) void conv_pack_kernel(PackJobs jobs) {
   const PackJob& J = jobs.j[blockIdx.y];
   if (blockIdx.y >= jobs.n) return;
-  const int nf = J.cout * nch_of(J.cin) * 32;
-  const int nb = J.bwd ? J.cin * nch_of(J.cout) * 32 : 0;
+  const int nf = J.cout * conv_nch(J.cin) * 32;
+  const int nb = J.bwd ? J.cin * conv_nch(J.cout) * 32 : 0;
   for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < nf + nb; e += gridDim.x * blockDim.x) {
     if (e < nf) {
-      const int co = e / (nch_of(J.cin) * 32), r = e % (nch_of(J.cin) * 32);
+      const int co = e / (conv_nch(J.cin) * 32), r = e % (conv_nch(J.cin) * 32);
       const int c = r / 32, k = r % 32;
       int tap, ci;
       if (J.cin == 16) { tap = 2 * c + k / 16; ci = k % 16; }
@@ -1629,7 +1549,7 @@ __global__ __launch_bounds__(256) void conv_pack_kernel(PackJobs jobs) {
     } else {
       // dgrad: out channel = original ci, input channel = original co, tap flipped
       const int f = e - nf;
-      const int ci = f / (nch_of(J.cout) * 32), r = f % (nch_of(J.cout) * 32);
+      const int ci = f / (conv_nch(J.cout) * 32), r = f % (conv_nch(J.cout) * 32);
       const int c = r / 32, k = r % 32;
       int tap, co;
       if (J.cout == 16) { tap = 2 * c + k / 16; co = k % 16; }
@@ -1677,7 +1597,7 @@ __global__ __launch_bounds__(256) void conv_pack_fp8_kernel(PackJobs8 jobs) {
     k = max(-30, min(30, k));
   }
   const float sc = ldexpf(1.f, k);
-  const int nch = J.cin == 16 ? 5 : 9;
+  const int nch = conv_nch(J.cin);
   for (int e = threadIdx.x; e < nch * 32; e += blockDim.x) {
     const int c = e / 32, kk = e % 32;
     int tap, ci;
@@ -1694,8 +1614,7 @@ __global__ __launch_bounds__(256) void conv_pack_fp8_kernel(PackJobs8 jobs) {
 
 // (bit planes are staged expanded: cin = 32)
 inline size_t fwd_smem(int cin, int imgs, int H, int W, int cout, bool pool, bool fp8 = false) {
-  const int pixb = fp8 ? cin + 8 : cin * 2 + 16;
-  size_t t = (((size_t)imgs * (H + 2) * (W + 2) * pixb) + 15) & ~(size_t)15;
+  size_t t = (((size_t)imgs * (H + 2) * (W + 2) * tile_pixb(cin, fp8)) + 15) & ~(size_t)15;
   if (pool) t += (size_t)imgs * H * W * (cout + 4) * 2;
   return t;
 }
@@ -1759,6 +1678,18 @@ int fwd_grid(int ngroups, const void* kfn, size_t sm) {
 
 }  // namespace
 
+// LAUNCH(CI, CO, B) of the forward / weight-gradient instantiation for the layer's (cin, cout, bit-plane input); ERR: returned for any other
+#define CONV_DISPATCH(LAUNCH, ERR)                                                          \
+  if (in_bits) {                                                                            \
+    if (cout == 16) LAUNCH(32, 16, true);                                                   \
+    else if (cout == 32) LAUNCH(32, 32, true);                                              \
+    else return ERR;                                                                        \
+  } else if (cin == 16 && cout == 16) LAUNCH(16, 16, false);                                \
+  else if (cin == 16 && cout == 32) LAUNCH(16, 32, false);                                  \
+  else if (cin == 32 && cout == 16) LAUNCH(32, 16, false);                                  \
+  else if (cin == 32 && cout == 32) LAUNCH(32, 32, false);                                  \
+  else return ERR;
+
 static int conv_fwd_launch(const void* x, int in_bits, int cin, int cout, const void* w,
                            const float* wscale, const float* bias, const void* add,
                            const void* mask_src, void* y, void* y_full, void* pool_idx, int N,
@@ -1778,16 +1709,19 @@ static int conv_fwd_launch(const void* x, int in_bits, int cin, int cout, const 
     const int grid = fwd_grid(ngroups, (const void*)kfn, sm); /* (raises the LDS limit) */  \
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(kThreads), sm, stream, a);                     \
   } while (0)
+  // the row kernels: one image per wave, so kRowImgs per workgroup iteration
+  auto launch_row = [&](void (*kfn)(ConvFwdArgs), size_t sm0) {
+    const int grid = fwd_grid((N + kRowImgs - 1) / kRowImgs, (const void*)kfn, sm0);
+    hipLaunchKernelGGL(kfn, dim3(grid), dim3(kThreads), sm0, stream, a);
+    return (int)hipGetLastError();
+  };
   // 17..32 pixels wide (config 4's 24 x 24), 16 channels: the WIDE row kernel
   if (in_bits && cout == 16 && W > 16 && W <= 32 && !fp8 && g_conv0_row && !add && !mask_src &&
       !relu_in && kLutBytes + (size_t)kRowImgs * H * W * 16 * 2 <= 160 * 1024) {
-    const size_t sm0 = kLutBytes + (pool ? (size_t)kRowImgs * H * W * 16 * 2 : 0);
-    const auto kfn = conv0_row_kernel<0, 16, true>;
-    const int grid = fwd_grid((N + kRowImgs - 1) / kRowImgs, (const void*)kfn, sm0);
     // (no work queue: on config 4 it measured 5.45 vs 5.85 M frames/s -- a faster learner
     // forward there leaves the acting-bound step slower, tools/gpu_r6_c0q.sh)
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(kThreads), sm0, stream, a);
-    return (int)hipGetLastError();
+    return launch_row(conv0_row_kernel<0, 16, true>,
+                      kLutBytes + (pool ? (size_t)kRowImgs * H * W * 16 * 2 : 0));
   }
   if (in_bits && (cout == 16 || cout == 32) && W == 16 && !fp8 && g_conv0_row && !add &&
       !mask_src && !relu_in) {
@@ -1795,22 +1729,12 @@ static int conv_fwd_launch(const void* x, int in_bits, int cin, int cout, const 
         kLutBytes + (pool ? (size_t)kRowImgs * H * 16 * conv0_ostr(cout, false) * 2 : 0);
     if (sm0 > 160 * 1024) return (int)hipErrorInvalidValue;
     const bool hb = H == 16;  // 16 x 16 maps: batched row loads
-    const auto kfn = cout == 16 ? (hb ? conv0_row16_kernel : conv0_row_kernel<0, 16>)
-                                : (hb ? conv0_row_kernel<16, 32> : conv0_row_kernel<0, 32>);
-    const int grid = fwd_grid((N + kRowImgs - 1) / kRowImgs, (const void*)kfn, sm0);
     if (hb) a.queue = mbk_work_queue(stream, kQueueConv0);
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(kThreads), sm0, stream, a);
-    return (int)hipGetLastError();
+    return launch_row(cout == 16 ? (hb ? conv0_row16_kernel : conv0_row_kernel<0, 16>)
+                                 : (hb ? conv0_row_kernel<16, 32> : conv0_row_kernel<0, 32>),
+                      sm0);
   }
-  if (in_bits) {
-    if (cout == 16) LAUNCH(32, 16, true);
-    else if (cout == 32) LAUNCH(32, 32, true);
-    else return (int)hipErrorInvalidValue;
-  } else if (cin == 16 && cout == 16) LAUNCH(16, 16, false);
-  else if (cin == 16 && cout == 32) LAUNCH(16, 32, false);
-  else if (cin == 32 && cout == 16) LAUNCH(32, 16, false);
-  else if (cin == 32 && cout == 32) LAUNCH(32, 32, false);
-  else return (int)hipErrorInvalidValue;
+  CONV_DISPATCH(LAUNCH, (int)hipErrorInvalidValue)
 #undef LAUNCH
   return (int)hipGetLastError();
 }
@@ -1837,18 +1761,6 @@ extern "C" int mbk_conv_fwd_fp8(const void* x, int in_bits, int cin, int cout, c
 extern "C" int mbk_conv_fwd_imgs(int in_bits, int cin, int cout, int H, int W, int pool, int fp8) {
   return fwd_imgs(cin, cout, H, W, in_bits != 0, pool != 0, fp8 != 0);
 }
-
-// LAUNCH(CI, CO, B) for the layer's (cin, cout, bit-plane input); ERR: returned for any other
-#define WGRAD_DISPATCH(LAUNCH, ERR)                                                         \
-  if (in_bits) {                                                                            \
-    if (cout == 16) LAUNCH(32, 16, true);                                                   \
-    else if (cout == 32) LAUNCH(32, 32, true);                                              \
-    else return ERR;                                                                        \
-  } else if (cin == 16 && cout == 16) LAUNCH(16, 16, false);                                \
-  else if (cin == 16 && cout == 32) LAUNCH(16, 32, false);                                  \
-  else if (cin == 32 && cout == 16) LAUNCH(32, 16, false);                                  \
-  else if (cin == 32 && cout == 32) LAUNCH(32, 32, false);                                  \
-  else return ERR;
 
 // the wgrad instantiation of (CI, CO, B) for this map width: band layout (WT = 8 / 16 / 24)
 // or the plain one; unpool: the stage-0 layer of a 16-wide map only (null otherwise)
@@ -1891,7 +1803,7 @@ extern "C" int mbk_conv_wgrad_parts(int in_bits, int cin, int cout, int N, int H
   const int nrounds = (N + imgs - 1) / imgs;
   const void* kq = nullptr;
 #define Q(CI, CO, B) kq = wgrad_kfn<CI, CO, B>(H, W, unpool)
-  WGRAD_DISPATCH(Q, -(int)hipErrorInvalidValue)
+  CONV_DISPATCH(Q, -(int)hipErrorInvalidValue)
 #undef Q
   if (!kq) return -(int)hipErrorInvalidValue;
   // the backward cap leaves room for one acting workgroup (80 KB of LDS) beside the learner's:
@@ -1930,7 +1842,7 @@ extern "C" int mbk_conv_wgrad(const void* x, int in_bits, int cin, int cout, con
     void* args[] = {&a};                                                                    \
     hipLaunchKernel(kfn, grid, dim3(kThreads), args, sm, stream);                           \
   } while (0)
-  WGRAD_DISPATCH(LAUNCH, (int)hipErrorInvalidValue)
+  CONV_DISPATCH(LAUNCH, (int)hipErrorInvalidValue)
 #undef LAUNCH
   return (int)hipGetLastError();
 }

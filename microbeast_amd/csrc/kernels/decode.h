@@ -1,7 +1,7 @@
 // Device helpers for decoding the engine's 16-bit cell codes on the GPU: the 78-bit action
-// mask of a cell (exactly the simulator's rules, include/microrts_rules.h) and the bit-plane
-// -> bf16 expansion of the stage-0 conv. Shared by obs_mask.hip (decode kernels) and
-// trunk.hip (the fused acting step, which decodes inside its conv trunk launch).
+// mask of a cell (exactly the simulator's rules, include/microrts_rules.h). Shared by
+// obs_mask.hip (decode kernels) and trunk.hip (the fused acting step, which decodes inside its
+// conv trunk launch).
 #pragma once
 #include "../include/microrts_rules.h"
 #include "common.h"
@@ -85,35 +85,6 @@ __device__ __forceinline__ void cell_mask(const uint16_t* cs, int c, int H, int 
   if (any_ret) setb3(w, kSegOff[0] + A_RETURN);
   if (any_prod) setb3(w, kSegOff[0] + A_PRODUCE);
   if (any_att) setb3(w, kSegOff[0] + A_ATTACK);
-}
-
-// 8 one-hot planes (the low byte of bits) -> 8 bf16 (1.0 / 0.0): one entry of the stage-0
-// conv's byte -> fragment lookup table (conv.hip conv0_row_kernel)
-__device__ __forceinline__ uint4 bits8_bf16(uint32_t bits) {
-  uint32_t w4[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    w4[j] = (((bits >> (2 * j)) & 1u) ? 0x3F80u : 0u) |
-            (((bits >> (2 * j + 1)) & 1u) ? 0x3F800000u : 0u);
-  return make_uint4(w4[0], w4[1], w4[2], w4[3]);
-}
-
-// lane x <- lane x-1 / x+1 inside each 16-lane DPP row, zero at the row ends (the stage-0
-// conv's zero padding for its kx = 0 / 2 taps)
-__device__ __forceinline__ uint32_t dpp_shr1_zero(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x111, 0xF, 0xF, true);
-}
-__device__ __forceinline__ uint32_t dpp_shl1_zero(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x101, 0xF, 0xF, true);
-}
-// the same for floats with -inf at the row ends (max-pool padding)
-__device__ __forceinline__ float dpp_shr1_ninf(float v) {
-  return __int_as_float(
-      __builtin_amdgcn_update_dpp((int)0xFF800000u, __float_as_int(v), 0x111, 0xF, 0xF, false));
-}
-__device__ __forceinline__ float dpp_shl1_ninf(float v) {
-  return __int_as_float(
-      __builtin_amdgcn_update_dpp((int)0xFF800000u, __float_as_int(v), 0x101, 0xF, 0xF, false));
 }
 
 }  // namespace mbk

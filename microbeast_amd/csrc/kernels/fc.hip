@@ -28,16 +28,6 @@ constexpr int R = 128;          // K rows per LDS stage
 constexpr int GROW = OC * 2;    // g tile row bytes
 constexpr int XROW = IC * 2;    // x tile row bytes
 
-// relu of 8 packed bf16 (sign bit set -> 0)
-__device__ __forceinline__ uint4 relu8_sel(uint4 v) {
-  uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    w[j] = ((w[j] & 0x8000u) ? 0u : (w[j] & 0xFFFFu)) |
-           ((w[j] & 0x80000000u) ? 0u : (w[j] & 0xFFFF0000u));
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
 // element e of the staged tile rows [r, r+R) x cols [c0, c0+W) of a row-major bf16 [N][ld]
 // matrix (16 bytes: 8 columns of one row), zero-filled outside it
 template <int W, bool VEC>

@@ -43,15 +43,6 @@ constexpr int BK = 64;              // K step: two 32-wide MFMA K blocks
 constexpr int ROWB = BK * 2 + 16;   // LDS row bytes (16-byte pad: conflict-free b128 reads)
 constexpr int kMaxPairs = 16;
 
-__device__ __forceinline__ uint4 relu8_sel(uint4 v) {
-  uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    w[j] = ((w[j] & 0x8000u) ? 0u : (w[j] & 0xFFFFu)) |
-           ((w[j] & 0x80000000u) ? 0u : (w[j] & 0xFFFF0000u));
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
 // keep v's bf16 halves where the mask's bf16 halves are > 0
 __device__ __forceinline__ uint4 mask8(uint4 v, uint4 m) {
   const uint32_t mw[4] = {m.x, m.y, m.z, m.w};

@@ -25,10 +25,7 @@
 #include "tile.h"
 #include "decode.h"
 
-
 #include <algorithm>
-#include <cstdlib>
-#include <string>
 
 using namespace mbk;
 
@@ -36,14 +33,6 @@ namespace {
 
 constexpr int kThreads = 512;  // 8 waves: 2 per SIMD even at one workgroup per CU
 constexpr int kMaxTNI = 16;  // images per workgroup iteration (host picks <= this)
-constexpr int kWBufBytes = 32 * (9 * 64 + 16);  // one staged layer (largest: 32x32)
-
-template <int C>
-struct TG {
-  static constexpr int PIXB = C * 2 + 16;
-  static constexpr int PIXB8 = C + 8;  // fp8 (e4m3) tile pixel stride, as conv.hip's fp8 tile
-  static constexpr int NCH = C == 16 ? 5 : 9;
-};
 
 // zero the halo ring of a halo'd tile [nimg][(H+2)][(W+2)] of PIXB-byte pixels (index math
 // by float reciprocals: exact for these tiny ranges, no runtime integer division); 16-byte
@@ -71,47 +60,9 @@ __device__ __forceinline__ void zero_halo(char* t, int nimg, int H, int W) {
   }
 }
 
-// 4 floats -> 4 OCP e4m3 bytes, round-to-nearest-even saturated to +-448 (conv.hip's
-// cvt_fp8x4: the per-layer fp8 kernel's staging conversion, so the fused fp8 trunk matches it)
-__device__ __forceinline__ uint32_t fp8x4(float a, float b, float c, float d) {
-  auto sat = [](float v) { return fminf(fmaxf(v, -448.f), 448.f); };
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(sat(a), sat(b), 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(sat(c), sat(d), w, true);
-  return (uint32_t)w;
-}
-// 4 bf16 (two packed words) -> e4m3, optionally through relu
-__device__ __forceinline__ uint32_t bf16x4_fp8(uint2 o, bool relu) {
-  if (relu) o = make_uint2(relu2(o.x), relu2(o.y));
-  return fp8x4(lo_f(o.x), hi_f(o.x), lo_f(o.y), hi_f(o.y));
-}
-
 // conv3x3 (pad 1) of a halo'd LDS tile. Output either into a halo'd tile (with optional
 // in-place residual add from the same tile) or into a dense bf16 staging [nimg][H][W][COUT]
 // (for the pool). relu_in applies to the input fragments.
-// A layer's packed weights [COUT][NCH][32] bf16 live in LDS with each output row padded
-// by 16 bytes (row stride NCH*64 + 16: the 16 rows a wave reads hit distinct banks).
-template <int CIN>
-__device__ __forceinline__ int wrow_bytes() { return TG<CIN>::NCH * 64 + 16; }
-
-constexpr int kWRegs = 3;  // uint4 per thread to stage the largest layer (32x9x32 bf16)
-
-// global -> registers (issued early, overlapping the current conv)
-__device__ __forceinline__ void wload(const bf16* __restrict__ gw, int n16, uint4 r[kWRegs]) {
-#pragma unroll
-  for (int k = 0; k < kWRegs; ++k) {
-    const int e = threadIdx.x + k * kThreads;
-    r[k] = e < n16 ? ((const uint4*)gw)[e] : make_uint4(0, 0, 0, 0);
-  }
-}
-// registers -> padded LDS rows
-__device__ __forceinline__ void wstore(char* lw, int n16, int nch, const uint4 r[kWRegs]) {
-  const int per_row = nch * 4, stride = nch * 64 + 16;
-#pragma unroll
-  for (int k = 0; k < kWRegs; ++k) {
-    const int e = threadIdx.x + k * kThreads;
-    if (e < n16) *(uint4*)(lw + (e / per_row) * stride + (e % per_row) * 16) = r[k];
-  }
-}
 
 // The whole dynamic LDS of trunk_tail_kernel. conv_lds below is noinline (see there), so it
 // must address the tiles through this LDS array with 32-bit offsets: a generic char*
@@ -124,6 +75,33 @@ extern __shared__ __attribute__((aligned(16))) char trunk_smem[];
 // to every one of U's 9 tap reads (bit-identical: relu commutes with the bf16 rounding)
 enum ConvOut : int { OUT_TILE = 0, OUT_TILE_ADD = 1, OUT_STAGE = 2, OUT_TILE_RELU = 3 };
 
+// A conv's output step for one lane: v = the 4 channels co0 .. co0 + 3 (bias added) of tile-local
+// pixel m, whose slot in a halo'd tile is pixel index pix. MODE OUT_STAGE: bf16 into the dense
+// staging [m][COUT] at out; else into the halo'd bf16 tile at out -- OUT_TILE_ADD adds the
+// tile's own value first (the residual, in place), OUT_TILE_RELU stores relu(v). F8 (fp8 trunk):
+// OUT_TILE_RELU writes fp8(relu(bf16(v))) into the fp8 tile at out instead, and the other tile
+// modes copy the stored value as fp8 into the fp8 tile at out8 for cp = 1 (relu'd) / 2 (as is).
+template <int COUT, int MODE, bool F8>
+__device__ __forceinline__ void conv_store(float (&v)[4], int m, int pix, int co0, int out,
+                                           int out8 = 0, int cp = 0) {
+  constexpr int PO = (F8 && MODE == OUT_TILE_RELU) ? Geo<COUT>::PIXB8 : Geo<COUT>::PIXB;
+  if constexpr (MODE == OUT_STAGE) {
+    *(uint2*)(trunk_smem + out + (m * COUT + co0) * 2) =
+        make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
+  } else if constexpr (F8 && MODE == OUT_TILE_RELU) {
+    *(uint32_t*)(trunk_smem + out + pix * PO + co0) =
+        bf16x4_fp8(make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3])), true);
+  } else {
+    char* p = trunk_smem + out + (pix * PO + co0 * 2);
+    if constexpr (MODE == OUT_TILE_ADD) add_bf16x4(v, *(const uint2*)p);
+    uint2 o = make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
+    if constexpr (MODE == OUT_TILE_RELU) o = make_uint2(relu2(o.x), relu2(o.y));
+    *(uint2*)p = o;
+    if constexpr (F8)
+      if (cp) *(uint32_t*)(trunk_smem + out8 + pix * Geo<COUT>::PIXB8 + co0) = bf16x4_fp8(o, cp == 1);
+  }
+}
+
 constexpr int kWFrag = 18;  // this lane's weight fragments of the largest layer (9 x 2)
 
 // A lane's packed-weight fragments of tail layer l, (chunk c, block nb) at c * NB + nb.
@@ -134,7 +112,7 @@ __device__ __forceinline__ void wfetch(const bf16* gw, int cin, int cout, uint4 
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   typedef const __attribute__((address_space(1))) u32x4* GU4;
   const int lane = threadIdx.x & 63, g = lane >> 4, li = lane & 15;
-  const int nch = cin == 16 ? TG<16>::NCH : TG<32>::NCH, nb = cout / 16;
+  const int nch = cin == 16 ? Geo<16>::NCH : Geo<32>::NCH, nb = cout / 16;
 #pragma unroll
   for (int k = 0; k < kWFrag; ++k) {
     const int c = k / 2, b = k % 2;  // fixed (c, nb) slot layout: c * 2 + nb
@@ -149,7 +127,7 @@ __device__ __forceinline__ void wfetch(const bf16* gw, int cin, int cout, uint4 
 __device__ __forceinline__ void wfetch8(const uint8_t* gw, int cin, int cout, long w[kWFrag]) {
   typedef const __attribute__((address_space(1))) long* GL;
   const int lane = threadIdx.x & 63, g = lane >> 4, li = lane & 15;
-  const int nch = cin == 16 ? TG<16>::NCH : TG<32>::NCH, nb = cout / 16;
+  const int nch = cin == 16 ? Geo<16>::NCH : Geo<32>::NCH, nb = cout / 16;
 #pragma unroll
   for (int k = 0; k < kWFrag; ++k) {
     const int c = k / 2, b = k % 2;
@@ -163,25 +141,19 @@ __device__ __forceinline__ void wfetch8(const uint8_t* gw, int cin, int cout, lo
 //   MODE OUT_TILE_RELU writes fp8(relu(bf16(v))) into an fp8 tile (out, stride COUT + 8);
 //   MODE OUT_TILE_ADD writes the bf16 residual stream (out) and, for cp = 1 / 2, its fp8 copy
 //   relu'd / as is into the fp8 tile at out8 (the next conv's input).
-// WV (wave-owned tiles, act_trunk_w_kernel): 0 = the workgroup's waves share the tile's pixel
-// blocks (wave w takes blocks w, w + NW, ...); 1 = the calling wave alone runs every block of
-// its own images, two blocks per iteration; 2 = the same one block at a time (maps whose pixel
-// count is one block: no idle partner chain)
-template <int CIN, int COUT, bool RELU, int MODE, bool WLDS, bool F8 = false, int WV = 0>
+// The workgroup's waves share the tile's pixel blocks (wave w takes blocks w, w + NW, ...).
+template <int CIN, int COUT, bool RELU, int MODE, bool F8 = false>
 // in / out: byte offsets of halo'd tiles in trunk_smem (out of a MODE == OUT_STAGE call: a
-// dense bf16 staging [nimg][H][W][COUT]); weights: LDS offset (WLDS, rows of wstride bytes)
-// or this lane's fragments prefetched into registers by wfetch (wreg)
-__device__ __forceinline__ void conv_lds(int in, int H, int W, int nimg, int lw_off,
-                                         const uint4* wreg, int wstride,
+// dense bf16 staging [nimg][H][W][COUT]); weights: this lane's fragments prefetched into
+// registers by wfetch (wreg)
+__device__ __forceinline__ void conv_lds(int in, int H, int W, int nimg, const uint4* wreg,
                                          const float* __restrict__ bias, int out,
                                          const long* wreg8 = nullptr,
                                          const float* __restrict__ wscale = nullptr,
                                          int out8 = 0, int cp = 0) {
-  constexpr int NCH = TG<CIN>::NCH, NB = COUT / 16;
-  constexpr int PI = F8 ? TG<CIN>::PIXB8 : TG<CIN>::PIXB;
-  constexpr int PO = (F8 && MODE == OUT_TILE_RELU) ? TG<COUT>::PIXB8 : TG<COUT>::PIXB;
-  constexpr int PO8 = TG<COUT>::PIXB8;
-  static_assert(!(F8 && (RELU || WLDS)), "fp8 tiles are stored relu'd; weights from L2");
+  constexpr int NCH = Geo<CIN>::NCH, NB = COUT / 16;
+  constexpr int PI = F8 ? Geo<CIN>::PIXB8 : Geo<CIN>::PIXB;
+  static_assert(!(F8 && RELU), "fp8 tiles are stored relu'd");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int g = lane >> 4, li = lane & 15;
   const int Hp = H + 2, Wp = W + 2, HW = H * W;
@@ -192,10 +164,6 @@ __device__ __forceinline__ void conv_lds(int in, int H, int W, int nimg, int lw_
     if constexpr (F8) {
 #pragma unroll
       for (int c = 0; c < NCH; ++c) bw8[c][nb] = wreg8[c * 2 + nb];
-    } else if constexpr (WLDS) {
-      const int wr = lw_off + (nb * 16 + li) * wstride + g * 16;
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) bw[c][nb].u = *(const uint4*)(trunk_smem + wr + c * 64);
     } else {
 #pragma unroll
       for (int c = 0; c < NCH; ++c) bw[c][nb].u = wreg[c * 2 + nb];
@@ -237,34 +205,15 @@ __device__ __forceinline__ void conv_lds(int in, int H, int W, int nimg, int lw_
         else v[i] = acc[nb][i] + bv[nb][i];
       }
       const int pix = (px.im * Hp + px.y + 1) * Wp + px.x + 1;
-      if constexpr (MODE == OUT_STAGE) {
-        *(uint2*)(trunk_smem + out + (m * COUT + co0) * 2) =
-            make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
-      } else if constexpr (F8 && MODE == OUT_TILE_RELU) {
-        *(uint32_t*)(trunk_smem + out + pix * PO + co0) =
-            bf16x4_fp8(make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3])), true);
-      } else {
-        char* p = trunk_smem + out + (pix * PO + co0 * 2);
-        if constexpr (MODE == OUT_TILE_ADD) {
-          const uint2 ad = *(const uint2*)p;
-          v[0] += lo_f(ad.x); v[1] += hi_f(ad.x); v[2] += lo_f(ad.y); v[3] += hi_f(ad.y);
-        }
-        uint2 o = make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
-        if constexpr (MODE == OUT_TILE_RELU) o = make_uint2(relu2(o.x), relu2(o.y));
-        *(uint2*)p = o;
-        if constexpr (F8)
-          if (cp) *(uint32_t*)(trunk_smem + out8 + pix * PO8 + co0) = bf16x4_fp8(o, cp == 1);
-      }
+      conv_store<COUT, MODE, F8>(v, m, pix, co0, out, out8, cp);
     }
   };
-  constexpr int NJ = WV == 2 ? 1 : 2;  // independent block chains per iteration
-  const int pstart = WV ? 0 : wave;
-  constexpr int pstep = WV ? NJ : 2 * NW, poff = WV ? 1 : NW;
-  for (int pb0 = pstart; pb0 < nblk; pb0 += pstep) {
+  constexpr int NJ = 2;  // independent block chains per iteration
+  for (int pb0 = wave; pb0 < nblk; pb0 += 2 * NW) {
     int base[2];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      const int m = (pb0 + j * poff) * 16 + li;
+      const int m = (pb0 + j * NW) * 16 + li;
       const int mm = m < M ? m : 0;  // rows past M compute garbage that is never stored
       const Pix px = split(mm);
       base[j] = in + ((px.im * Hp + px.y) * Wp + px.x) * PI;
@@ -276,11 +225,7 @@ __device__ __forceinline__ void conv_lds(int in, int H, int W, int nimg, int lw_
       for (int nb = 0; nb < NB; ++nb) acc[j][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
-      int tap, ch0;
-      if (CIN == 16) { tap = 2 * c + (g >> 1); ch0 = 8 * (g & 1); }
-      else { tap = c; ch0 = 8 * g; }
-      const int tapc = tap < 9 ? tap : 8;
-      const int toff = ((tapc / 3) * Wp + (tapc % 3)) * PI + (F8 ? ch0 : ch0 * 2);
+      const int toff = chunk_off(CIN, c, g, Wp, PI, F8 ? 1 : 2);
       if constexpr (F8) {
         long a8[2];
 #pragma unroll
@@ -296,8 +241,7 @@ __device__ __forceinline__ void conv_lds(int in, int H, int W, int nimg, int lw_
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
         a[j].u = *(const uint4*)(trunk_smem + base[j] + toff);
-        if constexpr (RELU)
-          a[j].u = make_uint4(relu2(a[j].u.x), relu2(a[j].u.y), relu2(a[j].u.z), relu2(a[j].u.w));
+        if constexpr (RELU) a[j].u = relu8(a[j].u);
         // (CIN 16, tap 9 = the pad half of chunk 4: its packed weights are zero, so the
         // finite pixel read for it adds exactly 0 and needs no zeroing)
       }
@@ -308,14 +252,14 @@ __device__ __forceinline__ void conv_lds(int in, int H, int W, int nimg, int lw_
           acc[j][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw[c][nb].v, a[j].v, acc[j][nb], 0, 0, 0);
     }
     epilogue(pb0, acc[0]);
-    if constexpr (NJ == 2) epilogue(pb0 + poff, acc[1]);
+    epilogue(pb0 + NW, acc[1]);
   }
 }
 
 // One wave's conv over all of its own pixel blocks at once (the wave-owned acting tile): the
 // K-chunk loop is outside and the NBLK blocks (all the wave's pixels: NBLK * 16 >= M) inside,
 // so every chunk's weight fragment feeds NBLK independent accumulator chains and its LDS reads
-// issue together -- conv_lds WV = 1 ran two chains per iteration and paid the LDS latency, the
+// issue together -- a two-chains-per-iteration form paid the LDS latency, the
 // MFMA dependency and the epilogue once per block pair. Same taps, K order and epilogue maths
 // per output pixel as conv_lds (bit-identical). Pixel rows m >= M compute on pixel 0 and are not
 // stored.
@@ -326,8 +270,8 @@ __device__ __forceinline__ void conv_w(int in, int H, int W, int M, const uint4*
 #pragma unroll 1
   for (int pass = 0; pass < NPASS; ++pass) {
   const int jb = pass * NBLK;
-  constexpr int NCH = TG<CIN>::NCH, NB = COUT / 16;
-  constexpr int PI = TG<CIN>::PIXB, PO = TG<COUT>::PIXB;
+  constexpr int NCH = Geo<CIN>::NCH, NB = COUT / 16;
+  constexpr int PI = Geo<CIN>::PIXB;
   // an opaque lane index: every address below derives from it, so none of them is hoisted out
   // of the tile loop (LICM kept all phases' pixel offsets live across the whole tile: spills)
   int lane = threadIdx.x & 63;
@@ -362,13 +306,7 @@ __device__ __forceinline__ void conv_w(int in, int H, int W, int M, const uint4*
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) acc[j][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
   // chunk c's LDS byte offset (tap, 8-channel group of this lane)
-  auto toff = [&](int c) {
-    int tap, ch0;
-    if (CIN == 16) { tap = 2 * c + (g >> 1); ch0 = 8 * (g & 1); }
-    else { tap = c; ch0 = 8 * g; }
-    const int tapc = tap < 9 ? tap : 8;
-    return ((tapc / 3) * Wp + (tapc % 3)) * PI + ch0 * 2;
-  };
+  auto toff = [&](int c) { return chunk_off(CIN, c, g, Wp, PI, 2); };
   // software pipeline: chunk c+1's NBLK fragment reads are issued before chunk c's MFMAs, so the
   // LDS latency hides behind NBLK x NB MFMAs instead of stalling every block
   Frag8 fr[2][NBLK];
@@ -385,8 +323,7 @@ __device__ __forceinline__ void conv_w(int in, int H, int W, int M, const uint4*
 #pragma unroll
     for (int j = 0; j < NBLK; ++j) {
       Frag8 a = fr[c & 1][j];
-      if constexpr (RELU)
-        a.u = make_uint4(relu2(a.u.x), relu2(a.u.y), relu2(a.u.z), relu2(a.u.w));
+      if constexpr (RELU) a.u = relu8(a.u);
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb)
         acc[j][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw[c][nb].v, a.v, acc[j][nb], 0, 0, 0);
@@ -407,19 +344,7 @@ __device__ __forceinline__ void conv_w(int in, int H, int W, int M, const uint4*
       float v[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) v[i] = acc[j][nb][i] + bv[nb][i];
-      if constexpr (MODE == OUT_STAGE) {
-        *(uint2*)(trunk_smem + out + (m * COUT + co0) * 2) =
-            make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
-      } else {
-        char* p = trunk_smem + out + (pix * PO + co0 * 2);
-        if constexpr (MODE == OUT_TILE_ADD) {
-          const uint2 ad = *(const uint2*)p;
-          v[0] += lo_f(ad.x); v[1] += hi_f(ad.x); v[2] += lo_f(ad.y); v[3] += hi_f(ad.y);
-        }
-        uint2 o = make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
-        if constexpr (MODE == OUT_TILE_RELU) o = make_uint2(relu2(o.x), relu2(o.y));
-        *(uint2*)p = o;
-      }
+      conv_store<COUT, MODE, false>(v, m, pix, co0, out);
     }
   }
   }
@@ -430,16 +355,16 @@ __device__ __forceinline__ void conv_w(int in, int H, int W, int M, const uint4*
 template <int C, bool F8 = false, bool WV = false>
 __device__ __forceinline__ void pool_lds(const bf16* stg, int H, int W, int nimg, char* out,
                                          char* out8 = nullptr) {
-  constexpr int PO = TG<C>::PIXB, C4 = C / 4;
+  constexpr int PO = Geo<C>::PIXB, C4 = C / 4;
   const int Ho = (H + 1) >> 1, Wo = (W + 1) >> 1, HWo = Ho * Wo;
   const int tot = nimg * HWo * C4;
-  const float inv_hwo = 1.f / (float)HWo, inv_wo = 1.f / (float)Wo;
+  const PixSplit split{HWo, Wo, 1.f / (float)HWo, 1.f / (float)Wo};
   int e0 = WV ? (int)(threadIdx.x & 63) : (int)threadIdx.x;
   if (WV) asm volatile("" : "+v"(e0));  // opaque: not hoisted out of the acting tile loop
   for (int e = e0; e < tot; e += WV ? 64 : kThreads) {
     const int c4 = e % C4, p = e / C4;  // C4: compile-time power of two
-    const int im = (int)(((float)p + 0.5f) * inv_hwo), r = p - im * HWo;
-    const int oy = (int)(((float)r + 0.5f) * inv_wo), ox = r - oy * Wo;
+    const Pix o = split(p);
+    const int im = o.im, oy = o.y, ox = o.x;
     float mx[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
     for (int ky = 0; ky < 3; ++ky) {
       const int yy = 2 * oy - 1 + ky;
@@ -453,9 +378,9 @@ __device__ __forceinline__ void pool_lds(const bf16* stg, int H, int W, int nimg
       }
     }
     const int pix = (im * (Ho + 2) + oy + 1) * (Wo + 2) + ox + 1;
-    const uint2 o = make_uint2(pack2(mx[0], mx[1]), pack2(mx[2], mx[3]));
-    *(uint2*)(out + pix * PO + c4 * 8) = o;
-    if constexpr (F8) *(uint32_t*)(out8 + pix * TG<C>::PIXB8 + c4 * 4) = bf16x4_fp8(o, true);
+    const uint2 v = make_uint2(pack2(mx[0], mx[1]), pack2(mx[2], mx[3]));
+    *(uint2*)(out + pix * PO + c4 * 8) = v;
+    if constexpr (F8) *(uint32_t*)(out8 + pix * Geo<C>::PIXB8 + c4 * 4) = bf16x4_fp8(v, true);
   }
 }
 
@@ -483,19 +408,6 @@ struct TrunkArgs {
 // layer l of the tail (0..13): CIN / COUT of the (16, 32, 32) trunk
 __device__ __forceinline__ int tail_cin(int l) { return l < 5 ? 16 : 32; }
 __device__ __forceinline__ int tail_cout(int l) { return l < 4 ? 16 : 32; }
-__device__ __forceinline__ int tail_n16(int l) {
-  return tail_cout(l) * TG<16>::NCH * 4 * (tail_cin(l) == 16 ? 1 : 0) +
-         tail_cout(l) * TG<32>::NCH * 4 * (tail_cin(l) == 32 ? 1 : 0);
-}
-
-__device__ __forceinline__ uint4 relu8_sel(uint4 v) {
-  uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    w[j] = ((w[j] & 0x8000u) ? 0u : (w[j] & 0xFFFFu)) |
-           ((w[j] & 0x80000000u) ? 0u : (w[j] & 0xFFFF0000u));
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
 
 // relu -> network.5 (256 hidden) -> relu -> critic on the group's X2 tile (halo'd NHWC in
 // LDS at x2): the same MFMA tiling, K order and value reduction as fc.hip fc_fwd_kernel<256>
@@ -503,7 +415,7 @@ __device__ __forceinline__ uint4 relu8_sel(uint4 v) {
 // blocks of 16 per wave), so f and v match the separate launch bit for bit.
 __device__ __forceinline__ void trunk_fc(const char* x2, int H2, int W2, int nimg, int img0,
                                          const TrunkArgs& a, float* vred) {
-  constexpr int O = 256, NBW = 4, PX = TG<32>::PIXB;
+  constexpr int O = 256, NBW = 4, PX = Geo<32>::PIXB;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int G = lane >> 4, li = lane & 15;
   const int half = wave >> 2, wq = wave & 3;
@@ -558,16 +470,15 @@ __device__ __forceinline__ void trunk_fc(const char* x2, int H2, int W2, int nim
 template <bool F8>
 __device__ __forceinline__ void load_input(const TrunkArgs& a, int img0, int nimg, char* x0,
                                            char* f) {
-  constexpr int PX = TG<16>::PIXB, PX8 = TG<16>::PIXB8;
+  constexpr int PX = Geo<16>::PIXB, PX8 = Geo<16>::PIXB8;
   const int H0 = a.H0, W0 = a.W0;
   const int tot = nimg * H0 * W0 * 2;  // 16-byte chunks
   const uint4* src = (const uint4*)(a.x + (size_t)img0 * H0 * W0 * 16);
-  const float ihw = 1.f / (float)(H0 * W0), iw = 1.f / (float)W0;
+  const PixSplit split{H0 * W0, W0, 1.f / (float)(H0 * W0), 1.f / (float)W0};
   for (int e = threadIdx.x; e < tot; e += kThreads) {
-    const int q = e & 1, p = e >> 1;
-    const int im = (int)(((float)p + 0.5f) * ihw), r = p - im * H0 * W0;
-    const int y = (int)(((float)r + 0.5f) * iw), x = r - y * W0;
-    const int pix = (im * (H0 + 2) + y + 1) * (W0 + 2) + x + 1;
+    const int q = e & 1;
+    const Pix px = split(e >> 1);
+    const int pix = (px.im * (H0 + 2) + px.y + 1) * (W0 + 2) + px.x + 1;
     const uint4 v = src[e];
     *(uint4*)(x0 + pix * PX + q * 16) = v;
     if constexpr (F8)
@@ -580,15 +491,14 @@ __device__ __forceinline__ void load_input(const TrunkArgs& a, int img0, int nim
 __device__ __forceinline__ void store_output(const TrunkArgs& a, int img0, int nimg, int H2,
                                              int W2, const char* x2) {
   if (!a.y) return;
-  constexpr int PX = TG<32>::PIXB;
+  constexpr int PX = Geo<32>::PIXB;
   const int tot = nimg * H2 * W2 * 4;
   uint4* dst = (uint4*)(a.y + (size_t)img0 * H2 * W2 * 32);
-  const float ihw = 1.f / (float)(H2 * W2), iw = 1.f / (float)W2;
+  const PixSplit split{H2 * W2, W2, 1.f / (float)(H2 * W2), 1.f / (float)W2};
   for (int e = threadIdx.x; e < tot; e += kThreads) {
-    const int q = e & 3, p = e >> 2;
-    const int im = (int)(((float)p + 0.5f) * ihw), r = p - im * H2 * W2;
-    const int y = (int)(((float)r + 0.5f) * iw), x = r - y * W2;
-    dst[e] = *(const uint4*)(x2 + ((im * (H2 + 2) + y + 1) * (W2 + 2) + x + 1) * PX + q * 16);
+    const int q = e & 3;
+    const Pix px = split(e >> 2);
+    dst[e] = *(const uint4*)(x2 + ((px.im * (H2 + 2) + px.y + 1) * (W2 + 2) + px.x + 1) * PX + q * 16);
   }
 }
 
@@ -610,7 +520,7 @@ __global__ __launch_bounds__(kThreads) void trunk_tail_kernel(TrunkArgs a) {
   wfetch(a.w[0], tail_cin(0), tail_cout(0), wnext);
   // phase helper: take layer l's prefetched weights, prefetch layer l+1 (wrapping to 0 for
   // the next group), run conv l
-#define TAIL_PHASE(l, CI, CO, RELU, MODE, IN, H_, W_, WBUF, OUT)                          \
+#define TAIL_PHASE(l, CI, CO, RELU, MODE, IN, H_, W_, OUT)                                \
   do {                                                                                      \
     uint4 wc[kWFrag];                                                                       \
     _Pragma("unroll") for (int k = 0; k < kWFrag; ++k) wc[k] = wnext[k];                    \
@@ -618,49 +528,48 @@ __global__ __launch_bounds__(kThreads) void trunk_tail_kernel(TrunkArgs a) {
       const int ln = ((l) + 1) % 14;                                                        \
       wfetch(a.w[ln], tail_cin(ln), tail_cout(ln), wnext);                                  \
     }                                                                                       \
-    conv_lds<CI, CO, RELU, MODE, false>(IN, H_, W_, nimg, 0, wc, TG<CI>::NCH * 64, a.b[l],  \
-                                        OUT);                                               \
+    conv_lds<CI, CO, RELU, MODE>(IN, H_, W_, nimg, wc, a.b[l], OUT);                        \
   } while (0)
   for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
     const int img0 = grp * TNI, nimg = min(TNI, a.N - img0);
     // ---- stage 0: X0 <- input (R1), U0 halo zero (R2)
     load_input<false>(a, img0, nimg, R1, nullptr);
-    zero_halo<TG<16>::PIXB>(R1, nimg, H0, W0);
-    zero_halo<TG<16>::PIXB>(R2, nimg, H0, W0);
+    zero_halo<Geo<16>::PIXB>(R1, nimg, H0, W0);
+    zero_halo<Geo<16>::PIXB>(R2, nimg, H0, W0);
     __syncthreads();
 #pragma unroll 1
     for (int rb = 0; rb < 2; ++rb) {
-      TAIL_PHASE(2 * rb, 16, 16, true, OUT_TILE_RELU, oR1, H0, W0, oWB[0], oR2);
+      TAIL_PHASE(2 * rb, 16, 16, true, OUT_TILE_RELU, oR1, H0, W0, oR2);
       __syncthreads();
-      TAIL_PHASE(2 * rb + 1, 16, 16, false, OUT_TILE_ADD, oR2, H0, W0, oWB[1], oR1);
+      TAIL_PHASE(2 * rb + 1, 16, 16, false, OUT_TILE_ADD, oR2, H0, W0, oR1);
       __syncthreads();
     }
     // ---- stage 1: conv 16->32 (staging in R2) -> pool -> X1 (R1)
-    TAIL_PHASE(4, 16, 32, false, OUT_STAGE, oR1, H0, W0, oWB[0], oR2);
+    TAIL_PHASE(4, 16, 32, false, OUT_STAGE, oR1, H0, W0, oR2);
     __syncthreads();
     pool_lds<32>((const bf16*)R2, H0, W0, nimg, R1);
-    zero_halo<TG<32>::PIXB>(R1, nimg, H1, W1);
+    zero_halo<Geo<32>::PIXB>(R1, nimg, H1, W1);
     __syncthreads();
-    zero_halo<TG<32>::PIXB>(R2, nimg, H1, W1);  // U1 layout (staging consumed)
+    zero_halo<Geo<32>::PIXB>(R2, nimg, H1, W1);  // U1 layout (staging consumed)
 #pragma unroll 1
     for (int rb = 0; rb < 2; ++rb) {
-      TAIL_PHASE(5 + 2 * rb, 32, 32, true, OUT_TILE_RELU, oR1, H1, W1, oWB[1], oR2);
+      TAIL_PHASE(5 + 2 * rb, 32, 32, true, OUT_TILE_RELU, oR1, H1, W1, oR2);
       __syncthreads();
-      TAIL_PHASE(6 + 2 * rb, 32, 32, false, OUT_TILE_ADD, oR2, H1, W1, oWB[0], oR1);
+      TAIL_PHASE(6 + 2 * rb, 32, 32, false, OUT_TILE_ADD, oR2, H1, W1, oR1);
       __syncthreads();
     }
     // ---- stage 2
-    TAIL_PHASE(9, 32, 32, false, OUT_STAGE, oR1, H1, W1, oWB[1], oR2);
+    TAIL_PHASE(9, 32, 32, false, OUT_STAGE, oR1, H1, W1, oR2);
     __syncthreads();
     pool_lds<32>((const bf16*)R2, H1, W1, nimg, R1);
-    zero_halo<TG<32>::PIXB>(R1, nimg, H2, W2);
+    zero_halo<Geo<32>::PIXB>(R1, nimg, H2, W2);
     __syncthreads();
-    zero_halo<TG<32>::PIXB>(R2, nimg, H2, W2);
+    zero_halo<Geo<32>::PIXB>(R2, nimg, H2, W2);
 #pragma unroll 1
     for (int rb = 0; rb < 2; ++rb) {
-      TAIL_PHASE(10 + 2 * rb, 32, 32, true, OUT_TILE_RELU, oR1, H2, W2, oWB[0], oR2);
+      TAIL_PHASE(10 + 2 * rb, 32, 32, true, OUT_TILE_RELU, oR1, H2, W2, oR2);
       __syncthreads();
-      TAIL_PHASE(11 + 2 * rb, 32, 32, false, OUT_TILE_ADD, oR2, H2, W2, oWB[1], oR1);
+      TAIL_PHASE(11 + 2 * rb, 32, 32, false, OUT_TILE_ADD, oR2, H2, W2, oR1);
       __syncthreads();
     }
 #undef TAIL_PHASE
@@ -705,16 +614,16 @@ __global__ __launch_bounds__(kThreads) void trunk_tail8_kernel(TrunkArgs a) {
     _Pragma("unroll") for (int k = 0; k < kWFrag; ++k) wc[k] = wnext[k];             \
     const int ln = ((l) + 1) % 14;                                                   \
     wfetch8(a.w8[ln], tail_cin(ln), tail_cout(ln), wnext);                           \
-    conv_lds<CI, CO, false, MODE, false, true>(IN, H_, W_, nimg, 0, nullptr, 0, a.b[l], \
-                                               OUT, wc, a.ws[l], oF, CP);            \
+    conv_lds<CI, CO, false, MODE, true>(IN, H_, W_, nimg, nullptr, a.b[l], OUT, wc,  \
+                                        a.ws[l], oF, CP);                            \
   } while (0)
   for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
     const int img0 = grp * TNI, nimg = min(TNI, a.N - img0);
     // ---- stage 0: X0 <- input (A), F <- fp8(relu(X0)); halos of A / U0 (B) / F
     load_input<true>(a, img0, nimg, A, F);
-    zero_halo<TG<16>::PIXB>(A, nimg, H0, W0);
-    zero_halo<TG<16>::PIXB8>(B, nimg, H0, W0);
-    zero_halo<TG<16>::PIXB8>(F, nimg, H0, W0);
+    zero_halo<Geo<16>::PIXB>(A, nimg, H0, W0);
+    zero_halo<Geo<16>::PIXB8>(B, nimg, H0, W0);
+    zero_halo<Geo<16>::PIXB8>(F, nimg, H0, W0);
     __syncthreads();
 #pragma unroll 1
     for (int rb = 0; rb < 2; ++rb) {
@@ -727,10 +636,10 @@ __global__ __launch_bounds__(kThreads) void trunk_tail8_kernel(TrunkArgs a) {
     TAIL8(4, 16, 32, OUT_STAGE, oF, H0, W0, oA, 0);
     __syncthreads();
     pool_lds<32, true>((const bf16*)A, H0, W0, nimg, B, F);
-    zero_halo<TG<32>::PIXB>(B, nimg, H1, W1);
-    zero_halo<TG<32>::PIXB8>(F, nimg, H1, W1);
+    zero_halo<Geo<32>::PIXB>(B, nimg, H1, W1);
+    zero_halo<Geo<32>::PIXB8>(F, nimg, H1, W1);
     __syncthreads();
-    zero_halo<TG<32>::PIXB8>(A, nimg, H1, W1);  // U1 layout (staging consumed)
+    zero_halo<Geo<32>::PIXB8>(A, nimg, H1, W1);  // U1 layout (staging consumed)
 #pragma unroll 1
     for (int rb = 0; rb < 2; ++rb) {
       TAIL8(5 + 2 * rb, 32, 32, OUT_TILE_RELU, oF, H1, W1, oA, 0);
@@ -742,10 +651,10 @@ __global__ __launch_bounds__(kThreads) void trunk_tail8_kernel(TrunkArgs a) {
     TAIL8(9, 32, 32, OUT_STAGE, oF, H1, W1, oA, 0);
     __syncthreads();
     pool_lds<32, true>((const bf16*)A, H1, W1, nimg, B, F);
-    zero_halo<TG<32>::PIXB>(B, nimg, H2, W2);
-    zero_halo<TG<32>::PIXB8>(F, nimg, H2, W2);
+    zero_halo<Geo<32>::PIXB>(B, nimg, H2, W2);
+    zero_halo<Geo<32>::PIXB8>(F, nimg, H2, W2);
     __syncthreads();
-    zero_halo<TG<32>::PIXB8>(A, nimg, H2, W2);
+    zero_halo<Geo<32>::PIXB8>(A, nimg, H2, W2);
 #pragma unroll 1
     for (int rb = 0; rb < 2; ++rb) {
       TAIL8(10 + 2 * rb, 32, 32, OUT_TILE_RELU, oF, H2, W2, oA, 0);
@@ -841,14 +750,12 @@ __device__ __forceinline__ float bf16_round(float v) { return lo_f(pack2(v, 0.f)
 __device__ __forceinline__ void act_conv0(const uint32_t* bits_img, const char* lut,
                                           const Frag8 bw[9], const float bias[4], char* x0,
                                           int im) {
-  constexpr int H0 = 8, W0 = 8, PX = TG<16>::PIXB;
+  constexpr int H0 = 8, W0 = 8, PX = Geo<16>::PIXB;
   int lane = threadIdx.x & 63;
   asm volatile("" : "+v"(lane));  // opaque: no address hoisted out of the caller's tile loop
   const int g = lane >> 4, li = lane & 15;
   const int sh = 8 * g;
-  struct R3 {
-    uint32_t l, c, h;
-  };
+  using R3 = Row3;
   auto row = [&](uint32_t b) {  // LUT offsets of pixels x-1, x, x+1 (this lane's plane byte)
     R3 r;  // one v_bfe_u32 per byte, as conv0_row_kernel
     r.c = __builtin_amdgcn_ubfe(b, (uint32_t)sh, 8u) * 16u;
@@ -914,7 +821,7 @@ constexpr int kActStamps = 21;
 // The acting trunk with the tile split by WAVE instead of by phase: wave w owns envs
 // 2w, 2w+1 of the 8-env tile (4 waves, 80 KB of LDS: two workgroups per CU, round 6) from
 // their sparse rows to their trunk output -- codes, decode,
-// stage-0 conv + pool, the 14 convs (conv_lds WV = 1 / 2 over its own images), the pools and
+// stage-0 conv + pool, the 14 convs (conv_w over its own images), the pools and
 // the halo zeroing -- in its own slices of the two regions, so the trunk needs no workgroup
 // barrier at all (LDS is in order within a wave). The phase-split form ran ~25 workgroup-wide
 // phases per tile with 2 waves per SIMD: every phase waited for its slowest wave, the 2x2 stage
@@ -943,7 +850,7 @@ constexpr int kWNW = 4;                                      // waves per workgr
 constexpr int kWThreads = 64 * kWNW;
 constexpr int kWEnv = 2;                                     // envs (images) per wave
 constexpr int kWTni = kWNW * kWEnv;                          // envs per tile
-constexpr int kWImgB = 10 * 10 * TG<16>::PIXB;               // largest per-image footprint (X0)
+constexpr int kWImgB = 10 * 10 * Geo<16>::PIXB;               // largest per-image footprint (X0)
 constexpr int kWSlice = kWEnv * kWImgB;                      // a wave's slice of R1 / R2
 constexpr int kWRegion = kWNW * kWSlice;                     // R1 = R2 = 38400 bytes
 constexpr int kWCnt = 2 * kWRegion;                          // [2][256] pair counts per cell
@@ -956,7 +863,7 @@ constexpr int kWSmem = kWLst + 2 * kWList * 4;
 // other's convs, and a learner workgroup of up to 80 KB can share the CU with one of them
 // (round 5's 16-env workgroups took 157 KB: a whole CU)
 static_assert(2 * kWSmem <= 160 * 1024, "two wave-owned acting workgroups per CU");
-static_assert(8 * 8 * 32 * 2 <= kWImgB && 6 * 6 * TG<32>::PIXB <= kWImgB, "stage footprints");
+static_assert(8 * 8 * 32 * 2 <= kWImgB && 6 * 6 * Geo<32>::PIXB <= kWImgB, "stage footprints");
 // a wave's decode scratch inside its R2 slice (dead once its stage-0 conv has run) with the
 // wave's own copy of the stage-0 byte -> 8 bf16 table behind it (written before each tile's
 // stage-0 conv: 4 LDS stores per lane, instead of a workgroup-wide 4 KB that no longer fits),
@@ -974,7 +881,7 @@ static_assert(kWList16 + kWEnv * kActS * 2 <= kWSlice, "decode mask scratch");
 // [hidden block][image] (mbk::crit_sum then adds the blocks in hidden order, as every FC)
 __device__ __forceinline__ void tile_fc(int nimg, int img0, const TrunkArgs& a,
                                         const uint4 wf[4][4], float* vred) {
-  constexpr int H2 = 2, W2 = 2, PX = TG<32>::PIXB, NKS = H2 * W2;
+  constexpr int H2 = 2, W2 = 2, PX = Geo<32>::PIXB, NKS = H2 * W2;
   int lane = threadIdx.x & 63;
   asm volatile("" : "+v"(lane));  // opaque: no address hoisted out of the tile loop
   const int wave = threadIdx.x >> 6;
@@ -1257,10 +1164,10 @@ __device__ __forceinline__ void act_trunk_w_kernel_body(const ActTrunkArgs& a) {
       // ---- stage-0 conv + pool of the wave's images into its X0 slice
       for (int i = lane; i < 256; i += 64)  // this wave's byte -> 8 bf16 table
         ((uint4*)(R2 + kWLut))[i] = mbk::bits8_bf16((uint32_t)i);
-      zero_halo<TG<16>::PIXB, true>(R1, nw, H0, W0);
+      zero_halo<Geo<16>::PIXB, true>(R1, nw, H0, W0);
       for (int j = 0; j < nw; ++j) act_conv0(lbits + j * S, lut, bw0, bias0, R1, j);
       __builtin_amdgcn_wave_barrier();
-      zero_halo<TG<16>::PIXB, true>(R2, nw, H0, W0);  // U0 layout (decode scratch is dead)
+      zero_halo<Geo<16>::PIXB, true>(R2, nw, H0, W0);  // U0 layout (decode scratch is dead)
       __builtin_amdgcn_wave_barrier();
       ACT_STAMP(3);
       // ---- stage 0 residual blocks, stages 1 and 2 on the wave's own images
@@ -1271,8 +1178,8 @@ __device__ __forceinline__ void act_trunk_w_kernel_body(const ActTrunkArgs& a) {
       }
       ACT_WPHASE(4, 16, 32, false, OUT_STAGE, 8, oR1, H0, W0, oR2);
       pool_lds<32, false, true>((const bf16*)R2, H0, W0, nw, R1);
-      zero_halo<TG<32>::PIXB, true>(R1, nw, H1, W1);
-      zero_halo<TG<32>::PIXB, true>(R2, nw, H1, W1);
+      zero_halo<Geo<32>::PIXB, true>(R1, nw, H1, W1);
+      zero_halo<Geo<32>::PIXB, true>(R2, nw, H1, W1);
       __builtin_amdgcn_wave_barrier();
 #pragma unroll 1
       for (int rb = 0; rb < 2; ++rb) {
@@ -1281,8 +1188,8 @@ __device__ __forceinline__ void act_trunk_w_kernel_body(const ActTrunkArgs& a) {
       }
       ACT_WPHASE(9, 32, 32, false, OUT_STAGE, 2, oR1, H1, W1, oR2);
       pool_lds<32, false, true>((const bf16*)R2, H1, W1, nw, R1);
-      zero_halo<TG<32>::PIXB, true>(R1, nw, H2, W2);
-      zero_halo<TG<32>::PIXB, true>(R2, nw, H2, W2);
+      zero_halo<Geo<32>::PIXB, true>(R1, nw, H2, W2);
+      zero_halo<Geo<32>::PIXB, true>(R2, nw, H2, W2);
       __builtin_amdgcn_wave_barrier();
 #pragma unroll 1
       for (int rb = 0; rb < 2; ++rb) {
@@ -1334,40 +1241,40 @@ __global__ __launch_bounds__(kWThreads, 2) void act_trunk_w_kernel(ActTrunkArgs 
 
 size_t region_bytes(int H0, int W0, int TNI) {
   const int H1 = (H0 + 1) / 2, W1 = (W0 + 1) / 2, H2 = (H1 + 1) / 2, W2 = (W1 + 1) / 2;
-  size_t r = (size_t)TNI * (H0 + 2) * (W0 + 2) * TG<16>::PIXB;                 // X0 / U0
+  size_t r = (size_t)TNI * (H0 + 2) * (W0 + 2) * Geo<16>::PIXB;                 // X0 / U0
   r = std::max(r, (size_t)TNI * H0 * W0 * 32 * 2);                            // stage-1 staging
-  r = std::max(r, (size_t)TNI * (H1 + 2) * (W1 + 2) * TG<32>::PIXB);          // X1 / U1
-  r = std::max(r, (size_t)TNI * (H2 + 2) * (W2 + 2) * TG<32>::PIXB);          // X2 / U2
+  r = std::max(r, (size_t)TNI * (H1 + 2) * (W1 + 2) * Geo<32>::PIXB);          // X1 / U1
+  r = std::max(r, (size_t)TNI * (H2 + 2) * (W2 + 2) * Geo<32>::PIXB);          // X2 / U2
   return (r + 15) & ~(size_t)15;
 }
 // fp8 trunk regions (see trunk_tail8_kernel): A, B and the fp8 conv-input tile F
 size_t trunk8_region_a(int H0, int W0, int TNI) {
   const int H1 = (H0 + 1) / 2, W1 = (W0 + 1) / 2, H2 = (H1 + 1) / 2, W2 = (W1 + 1) / 2;
-  size_t r = (size_t)TNI * (H0 + 2) * (W0 + 2) * TG<16>::PIXB;          // X0
+  size_t r = (size_t)TNI * (H0 + 2) * (W0 + 2) * Geo<16>::PIXB;          // X0
   r = std::max(r, (size_t)TNI * H0 * W0 * 32 * 2);                     // stage-1 staging
-  r = std::max(r, (size_t)TNI * (H1 + 2) * (W1 + 2) * TG<32>::PIXB8);  // U1
+  r = std::max(r, (size_t)TNI * (H1 + 2) * (W1 + 2) * Geo<32>::PIXB8);  // U1
   r = std::max(r, (size_t)TNI * H1 * W1 * 32 * 2);                     // stage-2 staging
-  r = std::max(r, (size_t)TNI * (H2 + 2) * (W2 + 2) * TG<32>::PIXB8);  // U2
+  r = std::max(r, (size_t)TNI * (H2 + 2) * (W2 + 2) * Geo<32>::PIXB8);  // U2
   return (r + 15) & ~(size_t)15;
 }
 size_t trunk8_region_b(int H0, int W0, int TNI) {
   const int H1 = (H0 + 1) / 2, W1 = (W0 + 1) / 2, H2 = (H1 + 1) / 2, W2 = (W1 + 1) / 2;
-  size_t r = (size_t)TNI * (H0 + 2) * (W0 + 2) * TG<16>::PIXB8;         // U0
-  r = std::max(r, (size_t)TNI * (H1 + 2) * (W1 + 2) * TG<32>::PIXB);   // X1
-  r = std::max(r, (size_t)TNI * (H2 + 2) * (W2 + 2) * TG<32>::PIXB);   // X2
+  size_t r = (size_t)TNI * (H0 + 2) * (W0 + 2) * Geo<16>::PIXB8;         // U0
+  r = std::max(r, (size_t)TNI * (H1 + 2) * (W1 + 2) * Geo<32>::PIXB);   // X1
+  r = std::max(r, (size_t)TNI * (H2 + 2) * (W2 + 2) * Geo<32>::PIXB);   // X2
   return (r + 15) & ~(size_t)15;
 }
 size_t trunk8_region_f(int H0, int W0, int TNI) {
   const int H1 = (H0 + 1) / 2, W1 = (W0 + 1) / 2;
-  size_t r = (size_t)TNI * (H0 + 2) * (W0 + 2) * TG<16>::PIXB8;
-  r = std::max(r, (size_t)TNI * (H1 + 2) * (W1 + 2) * TG<32>::PIXB8);
+  size_t r = (size_t)TNI * (H0 + 2) * (W0 + 2) * Geo<16>::PIXB8;
+  r = std::max(r, (size_t)TNI * (H1 + 2) * (W1 + 2) * Geo<32>::PIXB8);
   return (r + 15) & ~(size_t)15;
 }
-size_t trunk_smem_bytes(int H0, int W0, int TNI, size_t wb, bool f8) {
+size_t trunk_smem_bytes(int H0, int W0, int TNI, bool f8) {
   if (f8)
     return trunk8_region_a(H0, W0, TNI) + trunk8_region_b(H0, W0, TNI) +
            trunk8_region_f(H0, W0, TNI);
-  return 2 * region_bytes(H0, W0, TNI) + wb;
+  return 2 * region_bytes(H0, W0, TNI);
 }
 
 }  // namespace
@@ -1441,7 +1348,7 @@ static int trunk_launch(TrunkArgs a, int N, int H0, int W0, hipStream_t stream) 
   // for its weights, so more images amortise it) while keeping >= one group per CU
   const bool f8 = a.w8[0] != nullptr;
   int tni = 1;
-  while (tni < kMaxTNI && trunk_smem_bytes(H0, W0, tni * 2, 0, f8) <= 160 * 1024 &&
+  while (tni < kMaxTNI && trunk_smem_bytes(H0, W0, tni * 2, f8) <= 160 * 1024 &&
          (N + tni * 2 - 1) / (tni * 2) >= cus)
     tni *= 2;
   a.tni = tni;
@@ -1451,17 +1358,12 @@ static int trunk_launch(TrunkArgs a, int N, int H0, int W0, hipStream_t stream) 
   const size_t r = region_bytes(H0, W0, tni);
   a.r1_bytes = f8 ? (int)trunk8_region_a(H0, W0, tni) : (int)r;
   a.r2_bytes = f8 ? (int)trunk8_region_b(H0, W0, tni) : (int)r;
-  const size_t sm = trunk_smem_bytes(H0, W0, tni, 0, f8);
+  const size_t sm = trunk_smem_bytes(H0, W0, tni, f8);
   if (sm > 160 * 1024) return (int)hipErrorInvalidValue;
   const bool fc = a.f_out != nullptr;
   if (fc && f8) return (int)hipErrorInvalidValue;
   auto kfn = f8 ? trunk_tail8_kernel : fc ? trunk_tail_kernel<true> : trunk_tail_kernel<false>;
-  if (sm > 64 * 1024)
-    hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-  int per = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void*)kfn, kThreads, sm) !=
-          hipSuccess || per < 1)
-    per = 1;
+  const int per = mbk::blocks_per_cu((const void*)kfn, kThreads, sm);
   const int ngroups = (N + tni - 1) / tni;
   // persistent grid over the whole device
   const int grid = std::min(ngroups, cus * per);
